@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """Throughput bench of the VQ-VAE leaf hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N>1: either launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, one rank per GPU, or as the
      plain command above: with no WORLD_SIZE in the environment it starts its N ranks itself under torch.distributed.run on
      127.0.0.1 and a free port, passes the one JSON line of rank 0 through on its own stdout and returns the launcher's exit code)
 
-A step = one pass of the hot path over one 65,536-leaf batch per GPU, inputs resident in HBM.
+A step = one encode+quantize pass of the hot path over one 65,536-leaf batch per GPU, inputs resident in HBM.
 N = 1: BASELINE configs[1] ("1xMI355X, 1M synthetic leaves, fp32 encoder+quantizer" = 16 such batches, cycled for K steps).
-N > 1: BASELINE configs[3] ("leaves sharded across GPUs, 64M leaves" = 8 Mi leaves = 128 batches per GPU): the timed region
-       is max(K, 128) steps per rank so that every rank processes at least its configs[3] shard; `steps` in the JSON is the
-       number of steps really timed.
-`value` is encode+quantize leaves/s over all ranks; the decode leg is timed the same way and reported under "decode".
+`value` is encode+quantize leaves/s over all ranks, `ms_per_step` the wall time of one timed step; exactly K steps are timed.
+A plain run does only that: set up, W warm-up steps, K timed steps, the result line.
+--dump-outputs DIR: after the timed steps, rank 0 writes the indices its last step produced to DIR/indices.npy (float32).
+--full: every other leg as well, each timed or run after the headline steps:
+  the decode leg (timed like `value`, reported under "decode"), per-kernel profiles and rooflines, SOP-sized batch latencies,
+  the training legs (BASELINE configs[4]), the CPU oracle baseline with a parity spot check, the host-memory legs; and at
+  N > 1 BASELINE configs[3] ("leaves sharded across GPUs, 64M leaves" = 8 Mi leaves = 128 batches per GPU): the timed region
+  is max(K, 128) steps per rank so that every rank processes at least its configs[3] shard; `steps` in the JSON is the
+  number of steps really timed.
 Leaves shard across ranks with no data-path collective (weak scaling: per-GPU work is fixed).  PyTorch is used only for
 device memory, streams/events and the torch.distributed barrier.  Legs that go through host memory (end-to-end host-pointer
 calls, BASELINE configs[2] .vqvdb streaming decode) run in a PyTorch-free child process: vqvdb_amd/hostbench.py.
@@ -54,6 +59,20 @@ def timed(fn, steps, dist, device):
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     return (max_over_ranks(dt, device) if dist else dt), dt
+
+
+DUMP_MAX_BYTES = 60 << 20     # --dump-outputs stays below 64 MB
+
+
+def dump_outputs(path, idx):
+    """--dump-outputs: the [leaves, 64] codebook indices of the last timed step (what a caller of encode_device receives), as float32.
+    Batches above the size limit are cut to a fixed, seeded sample of rows."""
+    os.makedirs(path, exist_ok=True)
+    a = idx.cpu().numpy().astype(np.float32)
+    rows = DUMP_MAX_BYTES // (a.shape[1] * a.itemsize)
+    if len(a) > rows:
+        a = a[np.sort(np.random.default_rng(0).choice(len(a), rows, replace=False))]
+    np.save(os.path.join(path, "indices.npy"), a)
 
 
 def profile_pass(codec, fn, steps, device):
@@ -291,9 +310,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true", help="skip the training legs (BASELINE configs[4])")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-memory legs (host-pointer C ABI end to end; configs[2] .vqvdb streaming decode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the indices of the last timed step to DIR/indices.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="every leg beyond the headline encode figure (decode, profiles, rooflines, training, "
+                                                         "CPU baseline, host-memory legs, the configs[3] shard at N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline and parity spot check")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training legs (BASELINE configs[4])")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the host-memory legs (host-pointer C ABI end to end; configs[2] .vqvdb streaming decode)")
     ap.add_argument("--file-leaves", type=int, default=4 * 1024 * 1024, help="leaves in the configs[2] .vqvdb file")
     args = ap.parse_args()
     if args.gpus < 1:
@@ -370,8 +392,10 @@ def main():
     codec = _RehearsalCodec() if cpu_rehearsal else HipCodec(weightpack.dumps(W), device_id=dev_index)
     codec.set_chunk_leaves(BATCH)
 
-    # N > 1: every rank covers at least its configs[3] shard (8 Mi leaves = 128 batches)
-    steps = args.steps if world == 1 else max(args.steps, CONFIG3_LEAVES_PER_GPU // BATCH)
+    # N > 1 with --full: every rank covers at least its configs[3] shard (8 Mi leaves = 128 batches)
+    steps = max(args.steps, CONFIG3_LEAVES_PER_GPU // BATCH) if world > 1 and args.full else args.steps
+    if steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # synthetic leaves, uniform [0,1) (training data is [0,1]-normalised), resident in HBM; each
     # rank gets its own shard (different seed) -> no data-path collective.
@@ -392,188 +416,202 @@ def main():
 
     for s in range(max(args.warmup, 1)):
         enc(s)
-    for s in range(nb):            # make sure every index buffer is populated for the decode leg
-        enc(s)
-    for s in range(max(args.warmup, 1)):
-        dec(s)
+    if args.full:
+        for s in range(nb):            # make sure every index buffer is populated for the decode leg
+            enc(s)
+        for s in range(max(args.warmup, 1)):
+            dec(s)
     t_enc, t_enc_local = timed(enc, steps, dist, device)
-    t_dec, t_dec_local = timed(dec, steps, dist, device)
     enc_lps = world * steps * BATCH / t_enc
-    dec_lps = world * steps * BATCH / t_dec
-    per_rank = None
-    if dist:   # every rank's own rate (its own clock around its own steps): min / max show stragglers
-        objs = [None] * world
-        torch.distributed.all_gather_object(objs, (steps * BATCH / t_enc_local, steps * BATCH / t_dec_local))
-        per_rank = {"encode_leaves_per_s": [round(o[0], 1) for o in objs], "decode_leaves_per_s": [round(o[1], 1) for o in objs],
-                    "encode_min_max": [round(min(o[0] for o in objs), 1), round(max(o[0] for o in objs), 1)],
-                    "decode_min_max": [round(min(o[1] for o in objs), 1), round(max(o[1] for o in objs), 1)],
-                    "note": "leaves/s of each rank over its own wall time for the timed steps (barriers included); value uses the slowest rank's time"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx[(steps - 1) % nb])
+    if world == 1:
+        workload = f"BASELINE configs[1]: 1xMI355X, 1M synthetic leaves (16 x 65536-leaf batches, cycled for {steps} steps), fp32 encoder+quantizer, K=256 D=128"
+        if args.full:
+            workload += "; decode leg: the same batches' indices -> voxels, same K steps (roofline.decode_*)"
+    elif args.full:
+        workload = (f"BASELINE configs[3]: {world}xMI355X encode, leaves sharded across GPUs, {steps * BATCH} leaves per GPU "
+                    f"(>= the 8 Mi-leaf shard of the 64M-leaf job; 65536-leaf batches), fp32 encoder+quantizer, K=256 D=128")
+    else:
+        workload = f"{world}xMI355X encode, leaves sharded across GPUs, {steps * BATCH} leaves per GPU (65536-leaf batches), fp32 encoder+quantizer, K=256 D=128"
+    out = {
+        "metric": "8^3 leaves/s encode+quantize (decode reported under 'decode')",
+        "value": round(enc_lps, 1), "unit": "leaves/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
+        "ms_per_step": round(t_enc / steps * 1e3, 4), "timed_region_s": round(t_enc, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not cpu_rehearsal else "REHEARSAL on CPU with a stand-in codec: protocol test only, not a measurement",
+        "config": {"workload": workload,
+                   "leaves_per_step_per_gpu": BATCH, "leaves_per_gpu": steps * BATCH, "steps_requested": args.steps,
+                   "sharding": f"leaves sharded over {world} rank(s), no data-path collective"},
+    }
+    if args.full:     # every other leg, after the headline steps and in the order they always ran
+        t_dec, t_dec_local = timed(dec, steps, dist, device)
+        dec_lps = world * steps * BATCH / t_dec
+        per_rank = None
+        if dist:   # every rank's own rate (its own clock around its own steps): min / max show stragglers
+            objs = [None] * world
+            torch.distributed.all_gather_object(objs, (steps * BATCH / t_enc_local, steps * BATCH / t_dec_local))
+            per_rank = {"encode_leaves_per_s": [round(o[0], 1) for o in objs], "decode_leaves_per_s": [round(o[1], 1) for o in objs],
+                        "encode_min_max": [round(min(o[0] for o in objs), 1), round(max(o[0] for o in objs), 1)],
+                        "decode_min_max": [round(min(o[1] for o in objs), 1), round(max(o[1] for o in objs), 1)],
+                        "note": "leaves/s of each rank over its own wall time for the timed steps (barriers included); value uses the slowest rank's time"}
 
-    # Small-batch latency (position-split kernels): what the SOP's per-batch calls see (default 64, max 1024 encode / 8192
-    # decode leaves, SOP_VQVDB_Encoder.cpp:33-38).  Device-resident, rank 0 only.
-    small = None
-    if rank == 0 and not cpu_rehearsal:
-        small = {"note": "ms per call on the device at SOP-sized batches (position-split path); not the headline value"}
-        for nsm in (64, 1024, 8192):
-            for _ in range(3):
-                codec.encode_device(leaves[0].data_ptr(), nsm, idx[0].data_ptr(), stream)
-                codec.decode_device(idx[0].data_ptr(), nsm, rec.data_ptr(), stream)
-            t_e, _ = timed(lambda s: codec.encode_device(leaves[0].data_ptr(), nsm, idx[0].data_ptr(), stream), 10, False, device)
-            t_d, _ = timed(lambda s: codec.decode_device(idx[0].data_ptr(), nsm, rec.data_ptr(), stream), 10, False, device)
-            small[f"leaves_{nsm}"] = {"encode_ms": round(t_e / 10 * 1e3, 4), "decode_ms": round(t_d / 10 * 1e3, 4),
-                                      "encode_leaves_per_s": round(nsm * 10 / t_e, 1), "decode_leaves_per_s": round(nsm * 10 / t_d, 1)}
-        enc(0)   # idx[0] back to the full batch's indices for the parity spot check below
+        # Small-batch latency (position-split kernels): what the SOP's per-batch calls see (default 64, max 1024 encode / 8192
+        # decode leaves, SOP_VQVDB_Encoder.cpp:33-38).  Device-resident, rank 0 only.
+        small = None
+        if rank == 0 and not cpu_rehearsal:
+            small = {"note": "ms per call on the device at SOP-sized batches (position-split path); not the headline value"}
+            for nsm in (64, 1024, 8192):
+                for _ in range(3):
+                    codec.encode_device(leaves[0].data_ptr(), nsm, idx[0].data_ptr(), stream)
+                    codec.decode_device(idx[0].data_ptr(), nsm, rec.data_ptr(), stream)
+                t_e, _ = timed(lambda s: codec.encode_device(leaves[0].data_ptr(), nsm, idx[0].data_ptr(), stream), 10, False, device)
+                t_d, _ = timed(lambda s: codec.decode_device(idx[0].data_ptr(), nsm, rec.data_ptr(), stream), 10, False, device)
+                small[f"leaves_{nsm}"] = {"encode_ms": round(t_e / 10 * 1e3, 4), "decode_ms": round(t_d / 10 * 1e3, 4),
+                                          "encode_leaves_per_s": round(nsm * 10 / t_e, 1), "decode_leaves_per_s": round(nsm * 10 / t_d, 1)}
+            enc(0)   # idx[0] back to the full batch's indices for the parity spot check below
 
-    coll = (lambda nfl: f"all_reduce(SUM) of {nfl} fp32 over {world} rank(s), {'RCCL' if backend == 'nccl' else backend}") if dist else (lambda nfl: "none (1 rank)")
+        coll = (lambda nfl: f"all_reduce(SUM) of {nfl} fp32 over {world} rank(s), {'RCCL' if backend == 'nccl' else backend}") if dist else (lambda nfl: "none (1 rank)")
 
-    # Codebook (EMA) training steps, the quantizer part of BASELINE configs[4]: per-rank batches of 2048 leaves (the
-    # reference's BATCH_SIZE, python/training.py:49) and of 65536 leaves; statistics all-reduced over RCCL when N > 1.
-    train = None
-    if not args.no_train:
-        try:
-            from vqvdb_amd.codebook_training import CodebookTrainer
-            tcodec = HipCodec(weightpack.dumps(W), device_id=dev_index)   # its own handle: training rewrites the codebook
-            tcodec.set_chunk_leaves(BATCH)
-            trainer = CodebookTrainer(tcodec, device=str(device))
-            train = {"note": "VectorQuantizerEMA training-mode step on encoder outputs (encoder forward + latent + assign + "
-                             "statistics + all-reduce + EMA update); encoder/decoder weights frozen; not the headline value",
-                     "collective": coll(33281)}
-            ksteps = max(2, min(args.steps, 8))
-            for per_rank_b in (2048, BATCH):
-                x = leaves[0][:per_rank_b]
-                for _ in range(2):
-                    trainer.step(x, want_metrics=False)
-                t_tr, _ = timed(lambda s: trainer.step(x, want_metrics=False), ksteps, dist, device)
-                last = trainer.step(x)
-                train[f"per_rank_batch_{per_rank_b}"] = {"leaves_per_s": round(world * ksteps * per_rank_b / t_tr, 1),
-                                                          "ms_per_step": round(t_tr / ksteps * 1e3, 4), "steps": ksteps,
-                                                          "vq_loss": round(last["vq_loss"], 6), "perplexity": round(last["perplexity"], 3)}
-            tcodec.close()
-        except Exception as e:  # noqa: BLE001 — the training leg must never take the headline measurement down
-            train = {"error": f"{type(e).__name__}: {e}"}
+        # Codebook (EMA) training steps, the quantizer part of BASELINE configs[4]: per-rank batches of 2048 leaves (the
+        # reference's BATCH_SIZE, python/training.py:49) and of 65536 leaves; statistics all-reduced over RCCL when N > 1.
+        train = None
+        if not args.no_train:
+            try:
+                from vqvdb_amd.codebook_training import CodebookTrainer
+                tcodec = HipCodec(weightpack.dumps(W), device_id=dev_index)   # its own handle: training rewrites the codebook
+                tcodec.set_chunk_leaves(BATCH)
+                trainer = CodebookTrainer(tcodec, device=str(device))
+                train = {"note": "VectorQuantizerEMA training-mode step on encoder outputs (encoder forward + latent + assign + "
+                                 "statistics + all-reduce + EMA update); encoder/decoder weights frozen; not the headline value",
+                         "collective": coll(33281)}
+                ksteps = max(2, min(args.steps, 8))
+                for per_rank_b in (2048, BATCH):
+                    x = leaves[0][:per_rank_b]
+                    for _ in range(2):
+                        trainer.step(x, want_metrics=False)
+                    t_tr, _ = timed(lambda s: trainer.step(x, want_metrics=False), ksteps, dist, device)
+                    last = trainer.step(x)
+                    train[f"per_rank_batch_{per_rank_b}"] = {"leaves_per_s": round(world * ksteps * per_rank_b / t_tr, 1),
+                                                              "ms_per_step": round(t_tr / ksteps * 1e3, 4), "steps": ksteps,
+                                                              "vq_loss": round(last["vq_loss"], 6), "perplexity": round(last["perplexity"], 3)}
+                tcodec.close()
+            except Exception as e:  # noqa: BLE001 — the training leg must never take the headline measurement down
+                train = {"error": f"{type(e).__name__}: {e}"}
 
-    # Full training step (BASELINE configs[4]: fp32 VQ-VAE, AdamW on encoder/decoder, EMA codebook; global batch N x 2048):
-    # forward + backward + all-reduce of gradients (3.98 MB) and statistics (133 KB) + optimizer step.
-    full = None
-    if not args.no_train:
-        try:
-            from vqvdb_amd.full_training import FullTrainer
-            fcodec = HipCodec(weightpack.dumps(W), device_id=dev_index)
-            ftr = FullTrainer(fcodec, device=str(device))
-            full = {"note": "one optimizer step = training-mode forward (decoder stem through the per-step (tap, code) table, decoder tail folded) + backward of every layer + all-reduce + AdamW + EMA "
-                            "codebook update + rebuild of the weight-derived tables, fp32; not the headline value",
-                    "collective": coll("995905 + 33284"),
-                    "flop_per_leaf_nominal": 3 * (ENC_FLOP + DEC_FLOP), "flop_per_leaf_issued": TRAIN_ISSUED_FLOP,
-                    "frac_note": "whole_step_frac and by_class[*].frac count the FLOPs the step ISSUES on the matrix pipe (padding taps skipped, folded tail at its "
-                                 "folded cost; forward + data gradients + weight gradients, TRAIN_ISSUED_FLOP in bench.py) over the measured time / 157.3 TFLOP/s: "
-                                 "true utilisations, <= 1.  ratio_nominal_dense_* = 3 x the dense forward count of the reference ops over the same time: what the "
-                                 "algebraic eliminations buy, not a utilisation (it exceeds 1 at 8192 leaves per rank)",
-                    "streams": 1 if os.environ.get("VQHIP_TRAIN_STREAMS") == "1" else 2,
-                    "streams_note": "two streams: the data-gradient chain on the caller's stream, ending with the step's deferred reductions (bias sums, GroupNorm-affine "
-                                    "and attention-weight reductions as two multi-job launches, round 6); weight gradients, the codebook statistics (started beside the "
-                                    "decoder's forward) and the tail fold on the second. by_class times are event spans on either stream, they overlap, and "
-                                    "summed_event_spans_ms_per_step exceeds ms_per_step; whole_step_frac (from the wall time) is the utilisation of the step"}
-            ksteps = max(2, min(args.steps, 6))
-            for per_rank_b in (2048, 8192):
-                x = leaves[0][:per_rank_b]
-                for _ in range(2):
-                    ftr.step(x, want_metrics=False)
-                t_ft, _ = timed(lambda s: ftr.step(x, want_metrics=False), ksteps, dist, device)
-                last = ftr.step(x)
-                lps = world * ksteps * per_rank_b / t_ft
-                entry = {"leaves_per_s": round(lps, 1), "ms_per_step": round(t_ft / ksteps * 1e3, 4), "steps": ksteps,
-                         "loss": round(last["loss"], 6), "perplexity": round(last["perplexity"], 3),
-                         "whole_step_frac": round(lps / world * sum(TRAIN_ISSUED_FLOP.values()) / (PEAK_TF * 1e12), 4),
-                         "ratio_nominal_dense_to_fp32_mfma_peak": round(lps / world * 3 * (ENC_FLOP + DEC_FLOP) / (PEAK_TF * 1e12), 4)}
-                # (every rank runs the profiled steps: a step contains the gradient all-reduce)
-                by_class = train_step_classes(fcodec, lambda: ftr.step(x, want_metrics=False), per_rank_b, device)
-                if rank == 0:
-                    entry["by_class"] = by_class
-                full[f"per_rank_batch_{per_rank_b}"] = entry
-            fcodec.close()
-        except Exception as e:  # noqa: BLE001 — never take the headline measurement down
-            full = {"error": f"{type(e).__name__}: {e}"}
+        # Full training step (BASELINE configs[4]: fp32 VQ-VAE, AdamW on encoder/decoder, EMA codebook; global batch N x 2048):
+        # forward + backward + all-reduce of gradients (3.98 MB) and statistics (133 KB) + optimizer step.
+        full = None
+        if not args.no_train:
+            try:
+                from vqvdb_amd.full_training import FullTrainer
+                fcodec = HipCodec(weightpack.dumps(W), device_id=dev_index)
+                ftr = FullTrainer(fcodec, device=str(device))
+                full = {"note": "one optimizer step = training-mode forward (decoder stem through the per-step (tap, code) table, decoder tail folded) + backward of every layer + all-reduce + AdamW + EMA "
+                                "codebook update + rebuild of the weight-derived tables, fp32; not the headline value",
+                        "collective": coll("995905 + 33284"),
+                        "flop_per_leaf_nominal": 3 * (ENC_FLOP + DEC_FLOP), "flop_per_leaf_issued": TRAIN_ISSUED_FLOP,
+                        "frac_note": "whole_step_frac and by_class[*].frac count the FLOPs the step ISSUES on the matrix pipe (padding taps skipped, folded tail at its "
+                                     "folded cost; forward + data gradients + weight gradients, TRAIN_ISSUED_FLOP in bench.py) over the measured time / 157.3 TFLOP/s: "
+                                     "true utilisations, <= 1.  ratio_nominal_dense_* = 3 x the dense forward count of the reference ops over the same time: what the "
+                                     "algebraic eliminations buy, not a utilisation (it exceeds 1 at 8192 leaves per rank)",
+                        "streams": 1 if os.environ.get("VQHIP_TRAIN_STREAMS") == "1" else 2,
+                        "streams_note": "two streams: the data-gradient chain on the caller's stream, ending with the step's deferred reductions (bias sums, GroupNorm-affine "
+                                        "and attention-weight reductions as two multi-job launches, round 6); weight gradients, the codebook statistics (started beside the "
+                                        "decoder's forward) and the tail fold on the second. by_class times are event spans on either stream, they overlap, and "
+                                        "summed_event_spans_ms_per_step exceeds ms_per_step; whole_step_frac (from the wall time) is the utilisation of the step"}
+                ksteps = max(2, min(args.steps, 6))
+                for per_rank_b in (2048, 8192):
+                    x = leaves[0][:per_rank_b]
+                    for _ in range(2):
+                        ftr.step(x, want_metrics=False)
+                    t_ft, _ = timed(lambda s: ftr.step(x, want_metrics=False), ksteps, dist, device)
+                    last = ftr.step(x)
+                    lps = world * ksteps * per_rank_b / t_ft
+                    entry = {"leaves_per_s": round(lps, 1), "ms_per_step": round(t_ft / ksteps * 1e3, 4), "steps": ksteps,
+                             "loss": round(last["loss"], 6), "perplexity": round(last["perplexity"], 3),
+                             "whole_step_frac": round(lps / world * sum(TRAIN_ISSUED_FLOP.values()) / (PEAK_TF * 1e12), 4),
+                             "ratio_nominal_dense_to_fp32_mfma_peak": round(lps / world * 3 * (ENC_FLOP + DEC_FLOP) / (PEAK_TF * 1e12), 4)}
+                    # (every rank runs the profiled steps: a step contains the gradient all-reduce)
+                    by_class = train_step_classes(fcodec, lambda: ftr.step(x, want_metrics=False), per_rank_b, device)
+                    if rank == 0:
+                        entry["by_class"] = by_class
+                    full[f"per_rank_batch_{per_rank_b}"] = entry
+                fcodec.close()
+            except Exception as e:  # noqa: BLE001 — never take the headline measurement down
+                full = {"error": f"{type(e).__name__}: {e}"}
 
+        if rank == 0:
+            ek = profile_pass(codec, enc, min(steps, 16), device)
+            dk = profile_pass(codec, dec, min(steps, 16), device)
+            # spot parity: first 64 leaves of batch 0 vs the CPU oracle
+            parity = None
+            cpu = None
+            if not args.no_cpu_baseline:
+                cpu = cpu_baseline()
+                from oracle.oracle import Oracle
+                orc = Oracle(W, [t[0] for t in synth.TENSORS])
+                h = leaves[0][:64].cpu().numpy()
+                enc(0)
+                torch.cuda.synchronize(device)
+                gi = idx[0][:64].cpu().numpy()
+                oi = orc.encode(h, threads=usable_cpus())
+                parity = f"{int((gi == oi).all(axis=1).sum())}/64 sampled leaves index-exact vs CPU oracle"
+            host = None
+            if world == 1 and not args.no_host_path:
+                # free this process's big buffers first: the child holds its own workspace and an 8 GB leaf pool
+                torch.cuda.synchronize(device)
+                host = host_legs(args)
+            elif world > 1:
+                host = {"skipped": "host-memory legs run at N = 1 only (one process per GPU already saturates its PCIe link)"}
+            enc_roof, dec_roof = roofline_of(ek, ENC_FLOP, enc_lps / world), roofline_of(dk, DEC_FLOP, dec_lps / world)
+            dtail = next((k for k in dk if k["kernel"].startswith("dec_tail")), None)
+            # the decode half of the metric inside `roofline` too (the object a summariser keeps whole): BASELINE's metric is
+            # "encode+quantize AND decode"; `value` is the encode leg, these are the decode leg of the same run
+            enc_roof.update({
+                "decode_value": round(dec_lps, 1), "decode_unit": "leaves/s", "decode_ms_per_step": round(t_dec / steps * 1e3, 4),
+                "decode_kernel": dec_roof["kernel"], "decode_frac": dec_roof["frac"], "decode_achieved": dec_roof["achieved"],
+                "decode_avg_launch_ms": dec_roof["avg_launch_ms"],
+                "decode_whole_path_frac": dec_roof["whole_path_frac"], "decode_whole_path_frac_useful": dec_roof["whole_path_frac_useful"],
+                "dec_tail_ms": dtail["avg_ms"] if dtail else None,
+                "decode_traffic_bytes": dec_roof["whole_path_traffic_bytes"], "decode_traffic_stale": dec_roof["traffic_stale"],
+                "decode_workload": "decode of the same 65536-leaf index batches, resident in HBM, timed like `value` (K steps, barrier + synchronize on both sides)",
+            })
+            out.update({
+                # flat copies of the figures a summariser that drops nested objects would lose (the nested objects below stay authoritative)
+                "decode_value": round(dec_lps, 1), "decode_ms_per_step": round(t_dec / steps * 1e3, 4),
+                "roofline_frac": enc_roof["frac"], "decode_roofline_frac": dec_roof["frac"],
+                "whole_path_frac": enc_roof["whole_path_frac"], "decode_whole_path_frac": dec_roof["whole_path_frac"],
+                "whole_path_frac_useful": enc_roof["whole_path_frac_useful"], "decode_whole_path_frac_useful": dec_roof["whole_path_frac_useful"],
+                "dec_tail_ms": dtail["avg_ms"] if dtail else None, "dec_tail_issued_flop_per_leaf": dtail["issued_flop_per_leaf"] if dtail else None,
+                "traffic_stale": enc_roof["traffic_stale"], "decode_traffic_stale": dec_roof["traffic_stale"],
+                "n_devices_seen": len(devices_seen),
+                "per_rank_encode_min": per_rank["encode_min_max"][0] if per_rank else None, "per_rank_encode_max": per_rank["encode_min_max"][1] if per_rank else None,
+                "per_rank_decode_min": per_rank["decode_min_max"][0] if per_rank else None, "per_rank_decode_max": per_rank["decode_min_max"][1] if per_rank else None,
+                "collective_backend": ("nccl (RCCL)" if backend == "nccl" else backend) if dist else None,
+                "ranks_seen": ranks_seen,
+                "devices_seen": devices_seen,
+                "per_rank": per_rank,
+                "cpu_affinity": affinity,
+                "roofline": enc_roof,
+                "cpu_baseline": cpu,
+                "decode": {
+                    "value": round(dec_lps, 1), "unit": "leaves/s", "ms_per_step": round(t_dec / steps * 1e3, 4), "timed_region_s": round(t_dec, 4),
+                    "workload": "decode of 65536-leaf index batches resident in HBM (kernel path of BASELINE configs[2]; the file-level run is under 'config3')",
+                    "roofline": dec_roof,
+                },
+                "kernels": {"encode": ek, "decode": dk},
+                "flop_per_leaf": {"encode_nominal_dense": ENC_FLOP, "decode_nominal_dense": DEC_FLOP,
+                                  "encode_issued": sum(k["issued_flop_per_leaf"] for k in ek), "decode_issued": sum(k["issued_flop_per_leaf"] for k in dk)},
+                "parity_sample": parity,
+                "host_path": (host or {}).get("host_path") if host and "host_path" in host else host,
+                "config3": (host or {}).get("config3"),
+                "orchestrator_loop": (host or {}).get("orchestrator_loop"),
+                "host_process": (host or {}).get("process"),
+                "codebook_training": train,
+                "full_training": full,
+                "small_batch": small,
+            })
     if rank == 0:
-        ek = profile_pass(codec, enc, min(steps, 16), device)
-        dk = profile_pass(codec, dec, min(steps, 16), device)
-        # spot parity: first 64 leaves of batch 0 vs the CPU oracle
-        parity = None
-        cpu = None
-        if not args.no_cpu_baseline:
-            cpu = cpu_baseline()
-            from oracle.oracle import Oracle
-            orc = Oracle(W, [t[0] for t in synth.TENSORS])
-            h = leaves[0][:64].cpu().numpy()
-            enc(0)
-            torch.cuda.synchronize(device)
-            gi = idx[0][:64].cpu().numpy()
-            oi = orc.encode(h, threads=usable_cpus())
-            parity = f"{int((gi == oi).all(axis=1).sum())}/64 sampled leaves index-exact vs CPU oracle"
-        host = None
-        if world == 1 and not args.no_host_path:
-            # free this process's big buffers first: the child holds its own workspace and an 8 GB leaf pool
-            torch.cuda.synchronize(device)
-            host = host_legs(args)
-        elif world > 1:
-            host = {"skipped": "host-memory legs run at N = 1 only (one process per GPU already saturates its PCIe link)"}
-        enc_roof, dec_roof = roofline_of(ek, ENC_FLOP, enc_lps / world), roofline_of(dk, DEC_FLOP, dec_lps / world)
-        dtail = next((k for k in dk if k["kernel"].startswith("dec_tail")), None)
-        # the decode half of the metric inside `roofline` too (the object a summariser keeps whole): BASELINE's metric is
-        # "encode+quantize AND decode"; `value` is the encode leg, these are the decode leg of the same run
-        enc_roof.update({
-            "decode_value": round(dec_lps, 1), "decode_unit": "leaves/s", "decode_ms_per_step": round(t_dec / steps * 1e3, 4),
-            "decode_kernel": dec_roof["kernel"], "decode_frac": dec_roof["frac"], "decode_achieved": dec_roof["achieved"],
-            "decode_avg_launch_ms": dec_roof["avg_launch_ms"],
-            "decode_whole_path_frac": dec_roof["whole_path_frac"], "decode_whole_path_frac_useful": dec_roof["whole_path_frac_useful"],
-            "dec_tail_ms": dtail["avg_ms"] if dtail else None,
-            "decode_traffic_bytes": dec_roof["whole_path_traffic_bytes"], "decode_traffic_stale": dec_roof["traffic_stale"],
-            "decode_workload": "decode of the same 65536-leaf index batches, resident in HBM, timed like `value` (K steps, barrier + synchronize on both sides)",
-        })
-        out = {
-            "metric": "8^3 leaves/s encode+quantize (decode reported under 'decode')",
-            "value": round(enc_lps, 1), "unit": "leaves/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
-            "ms_per_step": round(t_enc / steps * 1e3, 4), "timed_region_s": round(t_enc, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic" if not cpu_rehearsal else "REHEARSAL on CPU with a stand-in codec: protocol test only, not a measurement",
-            "config": {"workload": (f"BASELINE configs[1]: 1xMI355X, 1M synthetic leaves (16 x 65536-leaf batches, cycled for {steps} steps), fp32 encoder+quantizer, K=256 D=128; decode leg: the same batches' indices -> voxels, same K steps (roofline.decode_*)" if world == 1 else
-                                    f"BASELINE configs[3]: {world}xMI355X encode, leaves sharded across GPUs, {steps * BATCH} leaves per GPU "
-                                    f"(>= the 8 Mi-leaf shard of the 64M-leaf job; 65536-leaf batches), fp32 encoder+quantizer, K=256 D=128"),
-                       "leaves_per_step_per_gpu": BATCH, "leaves_per_gpu": steps * BATCH, "steps_requested": args.steps,
-                       "sharding": f"leaves sharded over {world} rank(s), no data-path collective"},
-            # flat copies of the figures a summariser that drops nested objects would lose (the nested objects below stay authoritative)
-            "decode_value": round(dec_lps, 1), "decode_ms_per_step": round(t_dec / steps * 1e3, 4),
-            "roofline_frac": enc_roof["frac"], "decode_roofline_frac": dec_roof["frac"],
-            "whole_path_frac": enc_roof["whole_path_frac"], "decode_whole_path_frac": dec_roof["whole_path_frac"],
-            "whole_path_frac_useful": enc_roof["whole_path_frac_useful"], "decode_whole_path_frac_useful": dec_roof["whole_path_frac_useful"],
-            "dec_tail_ms": dtail["avg_ms"] if dtail else None, "dec_tail_issued_flop_per_leaf": dtail["issued_flop_per_leaf"] if dtail else None,
-            "traffic_stale": enc_roof["traffic_stale"], "decode_traffic_stale": dec_roof["traffic_stale"],
-            "n_devices_seen": len(devices_seen),
-            "per_rank_encode_min": per_rank["encode_min_max"][0] if per_rank else None, "per_rank_encode_max": per_rank["encode_min_max"][1] if per_rank else None,
-            "per_rank_decode_min": per_rank["decode_min_max"][0] if per_rank else None, "per_rank_decode_max": per_rank["decode_min_max"][1] if per_rank else None,
-            "collective_backend": ("nccl (RCCL)" if backend == "nccl" else backend) if dist else None,
-            "ranks_seen": ranks_seen,
-            "devices_seen": devices_seen,
-            "per_rank": per_rank,
-            "cpu_affinity": affinity,
-            "roofline": enc_roof,
-            "cpu_baseline": cpu,
-            "decode": {
-                "value": round(dec_lps, 1), "unit": "leaves/s", "ms_per_step": round(t_dec / steps * 1e3, 4), "timed_region_s": round(t_dec, 4),
-                "workload": "decode of 65536-leaf index batches resident in HBM (kernel path of BASELINE configs[2]; the file-level run is under 'config3')",
-                "roofline": dec_roof,
-            },
-            "kernels": {"encode": ek, "decode": dk},
-            "flop_per_leaf": {"encode_nominal_dense": ENC_FLOP, "decode_nominal_dense": DEC_FLOP,
-                              "encode_issued": sum(k["issued_flop_per_leaf"] for k in ek), "decode_issued": sum(k["issued_flop_per_leaf"] for k in dk)},
-            "parity_sample": parity,
-            "host_path": (host or {}).get("host_path") if host and "host_path" in host else host,
-            "config3": (host or {}).get("config3"),
-            "orchestrator_loop": (host or {}).get("orchestrator_loop"),
-            "host_process": (host or {}).get("process"),
-            "codebook_training": train,
-            "full_training": full,
-            "small_batch": small,
-        }
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if dist:
         torch.distributed.barrier()

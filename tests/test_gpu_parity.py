@@ -491,7 +491,7 @@ def test_bench_two_rank_code_path_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["VQ_BENCH_SINGLE_GPU_REHEARSAL"] = "1"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -506,6 +506,35 @@ def test_bench_two_rank_code_path_rehearsal():
     assert 0 < d["roofline"]["whole_path_frac"] <= 1 and 0 < d["decode"]["roofline"]["whole_path_frac"] <= 1
     ct = d["codebook_training"]
     assert "error" not in ct and "over 2 rank(s)" in ct["collective"] and ct["per_rank_batch_2048"]["leaves_per_s"] > 0
+
+
+def test_bench_plain_run_dumps_the_indices_of_its_last_step(codec, oracle, tmp_path):
+    """`python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR`: exactly the requested steps are timed, and DIR/indices.npy
+    holds what the last of them computed: batch 2 of the bench's seeded device inputs, regenerated here, encodes to the same indices
+    through a handle of this process, and its first 256 leaves to the CPU oracle's."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and "kernels" not in d and "decode" not in d
+    got = np.load(tmp_path / "indices.npy")
+    assert got.dtype == np.float32 and got.shape == (65536, 64)
+    gen = torch.Generator(device="cuda:0")
+    gen.manual_seed(1234)
+    batches = [torch.rand(65536, 512, device="cuda:0", dtype=torch.float32, generator=gen) for _ in range(3)]
+    x = batches[2].cpu().numpy()
+    want = codec.encode(x)
+    assert np.array_equal(got, want.astype(np.float32))
+    assert np.array_equal(want[:256], oracle.encode(x[:256], threads=8))
 
 
 def test_one_handle_mixed_batch_sizes_no_stale_state(pack, oracle):

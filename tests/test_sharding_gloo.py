@@ -80,7 +80,7 @@ def test_bench_n_gt_1_protocol_and_json_shape_without_a_gpu():
     import subprocess
     env = dict(os.environ, VQ_BENCH_CPU_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(29300 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1"]
+           "--master-port", str(29300 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -109,7 +109,7 @@ def test_bench_plain_command_starts_its_own_ranks():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["VQ_BENCH_CPU_REHEARSAL"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -123,6 +123,30 @@ def test_bench_plain_command_starts_its_own_ranks():
     assert bad.returncode != 0 and not [ln for ln in bad.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_plain_run_times_exactly_the_requested_steps_and_dumps_outputs(tmp_path):
+    """A plain `python bench.py --gpus 2 --steps 3` (no --full): exactly the requested steps are timed, the result line holds the
+    headline figure and nothing of the --full legs, and --dump-outputs writes the last step's indices as float32."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["VQ_BENCH_CPU_REHEARSAL"] = "1"
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "8^3 leaves/s encode+quantize (decode reported under 'decode')" and d["unit"] == "leaves/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["n_gpus"] == 2
+    assert d["steps"] == 3 and d["config"]["steps_requested"] == 3 and d["config"]["leaves_per_gpu"] == 3 * 65536
+    assert abs(d["ms_per_step"] * d["steps"] * 1e-3 * d["value"] - 2 * 3 * 65536) < 1e-3 * 2 * 3 * 65536
+    for key in ("roofline", "decode", "kernels", "cpu_baseline", "codebook_training", "full_training", "small_batch", "host_path"):
+        assert key not in d, key
+    a = np.load(out / "indices.npy")
+    assert a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 64
+
+
 def test_bench_eight_rank_rehearsal_matches_what_the_first_8_gpu_run_must_print():
     """`bench.py --gpus 8` as the driver launches it, eight gloo ranks with the CPU stand-in codec: ranks_seen == 8, eight distinct
     LOCAL_RANK -> device bindings, the ranks' CPU sets are a partition of this box's allowed cores (or no binding at all when there are
@@ -131,7 +155,7 @@ def test_bench_eight_rank_rehearsal_matches_what_the_first_8_gpu_run_must_print(
     import subprocess
     env = dict(os.environ, VQ_BENCH_CPU_REHEARSAL="1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-           "--master-port", str(29700 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "2"]
+           "--master-port", str(29700 + os.getpid() % 200), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -8,7 +8,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 steps = sys.argv[1] if len(sys.argv) > 1 else "24"
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "2", "--no-train", "--no-host-path", "--no-cpu-baseline"],
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", steps, "--warmup", "2", "--full", "--no-train", "--no-host-path", "--no-cpu-baseline"],
                    capture_output=True, text=True)
 if r.returncode != 0:
     sys.stderr.write(r.stderr[-2000:])

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Compile proof of INTEGRATION.md §2 against the reference's REAL factory (src/core/IVQVAECodec.{hpp,cpp}).
 
-Build container only: needs /root/reference (read-only; nothing of it is copied into this repository — the two files are copied to
-a temporary directory, patched there exactly as INTEGRATION.md §2 says, compiled with -DENABLE_HIP_BACKEND together with the
-adapter include/vqvdb_hip_backend.hpp, linked against vqvdb_amd/libvqvdb_hip.so, and the temporary directory is deleted).
+Compiling needs the reference checkout (read-only; $VQVDB_REFERENCE, or found beside the repository: find_reference()).
+Nothing of it is copied into this repository: the two files are copied to a temporary directory, patched there exactly as
+INTEGRATION.md §2 says, compiled with -DENABLE_HIP_BACKEND together with the adapter include/vqvdb_hip_backend.hpp, linked against
+vqvdb_amd/libvqvdb_hip.so, and the temporary directory is deleted.  Only the executables are kept.
 
 Checks:
   1. the patched reference factory + HipBackend compile and link (g++ -std=c++17 -Wall -Wextra, no warnings from our header);
@@ -22,8 +23,11 @@ Checks:
      ("no HIP device available"), i.e. after the embedded pack was found and parsed — never with "no weight pack given";
      a build without an embedded pack must fail with exactly that message.
 
-    python tools/prove_integration.py        -> exit code 0 and "integration proof: OK"
+    python tools/prove_integration.py                 -> compile into a temporary directory and run: exit code 0 and "integration proof: OK"
+    python tools/prove_integration.py --build DIR     -> compile only (__graft_entry__.build() -> oracle/ref_build.py: DIR = oracle/_ref/integration)
+    python tools/prove_integration.py --run DIR [--gpu]  -> run what --build compiled (no reference needed); --gpu: a device is present
 """
+import json
 import os
 import shutil
 import subprocess
@@ -31,7 +35,24 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src/core"
+
+
+def find_reference() -> str:
+    """The reference checkout: $VQVDB_REFERENCE, else a directory `reference` beside this repository or beside one of its parent
+    directories, else ~/reference.  The first candidate when none holds src/core (the caller then skips)."""
+    if os.environ.get("VQVDB_REFERENCE"):
+        return os.environ["VQVDB_REFERENCE"]
+    cands, d = [], ROOT
+    while os.path.dirname(d) != d:
+        d = os.path.dirname(d)
+        cands.append(os.path.join(d, "reference"))
+    cands.append(os.path.join(os.path.expanduser("~"), "reference"))
+    return next((c for c in cands if os.path.isdir(os.path.join(c, "src", "core"))), cands[0])
+
+
+REF_ROOT = find_reference()
+REF = os.path.join(REF_ROOT, "src", "core")
+LIB = os.path.join(ROOT, "vqvdb_amd", "libvqvdb_hip.so")
 
 MAIN = r'''
 #include <cstdio>
@@ -79,7 +100,7 @@ def sop_init_statements() -> list:
     through the patched create() call — what the SOP will execute to get its backend."""
     out = []
     for f in SOP_FILES:
-        t = open(os.path.join("/root/reference/src/SOP", f)).read()
+        t = open(os.path.join(REF_ROOT, "src", "SOP", f)).read()
         assert t.count(SOP_OLD) == 1, f"INTEGRATION.md §3 anchor not found exactly once in {f}"
         t = t.replace(SOP_OLD, SOP_NEW)
         a = t.index("CodecConfig config;")
@@ -103,101 +124,130 @@ int main() {
 '''
 
 
-def prove_sop_embedded(tmp: str, src: str, lib: str, env: dict) -> bool:
+# the SOP route executables: file name, what was compiled in, whether a pack is embedded
+SOP_BUILDS = [("sop_own_header", "weightpack --header, included by the adapter", True),
+              ("sop_own_object", "weightpack --header, linked as its own object", True),
+              ("sop_ref_tool", "reference convert_to_header.py --name g_vqhip_pack_data", True),
+              ("sop_no_pack", "no embedded pack in the build", False)]
+
+
+def tiny_pack() -> bytes:
+    """Parses; the device check comes before the shape validation (the same pack as tests/test_host_logic.py's _tiny_pack)."""
     sys.path.insert(0, ROOT)
     import numpy as np
     from vqvdb_amd import weightpack
-    pack = weightpack.dumps({"encoder.pre.0.bias": np.arange(16, dtype=np.float32)})   # parses; the device check comes before the shape validation
+    return weightpack.dumps({"encoder.pre.0.bias": np.arange(16, dtype=np.float32)})
+
+
+def build_sop_embedded(tmp: str, src: str, out: str) -> bool:
     fns = "".join("static bool sop_%d() {\n\t// %s, INTEGRATION.md §3 applied\n\t%s\n\treturn backend != nullptr;\n}\n" % (i, f, block)
                   for i, (f, block) in enumerate(sop_init_statements()))
     open(os.path.join(tmp, "sop_main.cpp"), "w").write(SOP_MAIN % fns)
     vqw = os.path.join(tmp, "model.vqw")
-    open(vqw, "wb").write(pack)
+    open(vqw, "wb").write(tiny_pack())
     own = os.path.join(tmp, "own")
     ref = os.path.join(tmp, "ref")
     os.makedirs(os.path.join(own, "bin"))
     os.makedirs(os.path.join(ref, "bin"))
     r = subprocess.run([sys.executable, "-m", "vqvdb_amd.weightpack", "--header", vqw, os.path.join(own, "bin", "vqhip_pack.h")], cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([sys.executable, "/root/reference/python/convert_to_header.py", vqw, os.path.join(ref, "bin", "vqhip_pack.h"), "--name", "g_vqhip_pack_data"],
+    r = subprocess.run([sys.executable, os.path.join(REF_ROOT, "python", "convert_to_header.py"), vqw, os.path.join(ref, "bin", "vqhip_pack.h"), "--name", "g_vqhip_pack_data"],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     obj = os.path.join(tmp, "vqhip_pack.o")
     subprocess.run(["gcc", "-x", "c", "-c", os.path.join(own, "bin", "vqhip_pack.h"), "-o", obj], check=True)
     base = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-DENABLE_HIP_BACKEND", "-I", src, "-I", os.path.join(src, "core"),
             os.path.join(src, "core", "IVQVAECodec.cpp"), os.path.join(tmp, "sop_main.cpp")]
-    link = ["-L" + os.path.dirname(lib), "-lvqvdb_hip", "-Wl,-rpath," + os.path.dirname(lib)]
-    builds = [("weightpack --header, included by the adapter", ['-DVQVDB_HIP_EMBEDDED_PACK_HEADER="bin/vqhip_pack.h"', "-I", own], True),
-              ("weightpack --header, linked as its own object", ["-DVQVDB_HIP_EMBEDDED_PACK", obj], True),
-              ("reference convert_to_header.py --name g_vqhip_pack_data", ['-DVQVDB_HIP_EMBEDDED_PACK_HEADER="bin/vqhip_pack.h"', "-I", ref], True),
-              ("no embedded pack in the build", [], False)]
+    link = ["-L" + os.path.dirname(LIB), "-lvqvdb_hip", "-Wl,-rpath," + os.path.dirname(LIB)]
+    extras = {"sop_own_header": ['-DVQVDB_HIP_EMBEDDED_PACK_HEADER="bin/vqhip_pack.h"', "-I", own],
+              "sop_own_object": ["-DVQVDB_HIP_EMBEDDED_PACK", obj],
+              "sop_ref_tool": ['-DVQVDB_HIP_EMBEDDED_PACK_HEADER="bin/vqhip_pack.h"', "-I", ref],
+              "sop_no_pack": []}
     ok = True
-    for name, extra, embedded in builds:
-        exe = os.path.join(tmp, "sop_proof")
-        r = subprocess.run(base + extra + ["-o", exe] + link, capture_output=True, text=True)
+    for exe, name, _ in SOP_BUILDS:
+        r = subprocess.run(base + extras[exe] + ["-o", os.path.join(out, exe)] + link, capture_output=True, text=True)
         if r.returncode != 0:
             print(r.stderr[-3000:])
             print(f"  SOP route [{name}]: FAILED to compile/link")
             ok = False
-            continue
-        r = subprocess.run([exe], capture_output=True, text=True, env=env)
-        msgs = [ln for ln in r.stderr.splitlines() if ln.startswith("Failed to create VQ-VAE backend:")]
-        if embedded:
-            good = (len(msgs) == 2 and all("no HIP device available" in m for m in msgs)) or "backend=object" in r.stdout      # a GPU box would get as far as the shape validation
-            good = good and "no weight pack given" not in r.stderr
-        else:
-            good = len(msgs) == 2 and all("no weight pack given (embedded model absent from this build)" in m for m in msgs)
-        print(f"  SOP route [{name}]: {r.stdout.strip()} | {msgs[0] if msgs else r.stderr.strip()} -> {'ok' if good else 'FAILED'}")
-        ok = ok and good
+    # test_embedded_model_builds_link_and_reach_the_device: leaf_harness with a header written by the reference's own generator
+    from vqvdb_amd.build import build_harness_embedded
+    build_harness_embedded(tiny_pack(), os.path.join(out, "harness_ref_tool"), "header", os.path.join(REF_ROOT, "python", "convert_to_header.py"))
     return ok
 
 
-def main() -> int:
-    if not os.path.isdir(REF):
-        print("integration proof: SKIPPED (no /root/reference here — this script runs in the build container only)")
-        return 0
-    lib = os.path.join(ROOT, "vqvdb_amd", "libvqvdb_hip.so")
-    if not os.path.exists(lib):
-        from vqvdb_amd.build import build
-        build()
+def build_proofs(out: str) -> bool:
+    """Compile the patched reference factory (+ MAIN) and the SOP route executables into `out`."""
+    sys.path.insert(0, ROOT)
+    from vqvdb_amd.build import build
+    build()
+    os.makedirs(out, exist_ok=True)
     tmp = tempfile.mkdtemp(prefix="vqhip_integration_")
     try:
         src = os.path.join(tmp, "src")
         os.makedirs(os.path.join(src, "core"))
         os.makedirs(os.path.join(src, "backends", "hip"))
         for f in ("IVQVAECodec.hpp", "IVQVAECodec.cpp"):
-            shutil.copy(os.path.join(REF, f), os.path.join(src, "core", f))
+            shutil.copyfile(os.path.join(REF, f), os.path.join(src, "core", f))      # contents only: the reference is read-only, the copy is patched
         shutil.copy(os.path.join(ROOT, "include", "vqvdb_hip.h"), os.path.join(src, "backends", "hip", "vqvdb_hip.h"))
         shutil.copy(os.path.join(ROOT, "include", "vqvdb_hip_backend.hpp"), os.path.join(src, "backends", "hip", "HipBackend.hpp"))
         patch_sources(src)
         open(os.path.join(tmp, "main.cpp"), "w").write(MAIN)
-        exe = os.path.join(tmp, "proof")
         cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-DENABLE_HIP_BACKEND", "-I", src, "-I", os.path.join(src, "core"),
-               os.path.join(src, "core", "IVQVAECodec.cpp"), os.path.join(tmp, "main.cpp"), "-o", exe,
-               "-L" + os.path.dirname(lib), "-lvqvdb_hip", "-Wl,-rpath," + os.path.dirname(lib)]
+               os.path.join(src, "core", "IVQVAECodec.cpp"), os.path.join(tmp, "main.cpp"), "-o", os.path.join(out, "proof"),
+               "-L" + os.path.dirname(LIB), "-lvqvdb_hip", "-Wl,-rpath," + os.path.dirname(LIB)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             print(r.stderr)
             print("integration proof: FAILED (compile/link)")
-            return 1
+            return False
         ours = [ln for ln in r.stderr.splitlines() if "HipBackend.hpp" in ln or "vqvdb_hip.h" in ln]
         if ours:
             print("\n".join(ours))
             print("integration proof: FAILED (warnings from the adapter headers)")
-            return 1
-        env = dict(os.environ, LD_LIBRARY_PATH="/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
-        r = subprocess.run([exe], capture_output=True, text=True, env=env)
-        print(r.stdout.strip())
-        print("stderr of the patched reference factory:\n  " + "\n  ".join(r.stderr.strip().splitlines()))
-        ok = (r.returncode == 0 and "hip_missing_pack=nullptr onnx_disabled=nullptr hip_cpu_device=nullptr" in r.stdout
-              and r.stderr.count("Failed to create VQ-VAE backend:") == 3 and "Model file not found at path: /nonexistent/model.vqw" in r.stderr)
-        ok = prove_sop_embedded(tmp, src, lib, env) and ok
-        print("integration proof: " + ("OK" if ok else "FAILED"))
-        return 0 if ok else 1
+            return False
+        return build_sop_embedded(tmp, src, out)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def run_proofs(out: str, gpu: bool = False) -> bool:
+    """Run what build_proofs compiled.  Without a device, the embedded builds must fail at the DEVICE ("no HIP device available");
+    with one (gpu=True), they get past it and the tiny pack is refused by the shape validation — never "no weight pack given"."""
+    env = dict(os.environ, LD_LIBRARY_PATH=os.path.dirname(LIB) + ":/opt/rocm/lib:" + os.environ.get("LD_LIBRARY_PATH", ""))
+    r = subprocess.run([os.path.join(out, "proof")], capture_output=True, text=True, env=env)
+    print(r.stdout.strip())
+    print("stderr of the patched reference factory:\n  " + "\n  ".join(r.stderr.strip().splitlines()))
+    ok = (r.returncode == 0 and "hip_missing_pack=nullptr onnx_disabled=nullptr hip_cpu_device=nullptr" in r.stdout
+          and r.stderr.count("Failed to create VQ-VAE backend:") == 3 and "Model file not found at path: /nonexistent/model.vqw" in r.stderr)
+    for exe, name, embedded in SOP_BUILDS:
+        r = subprocess.run([os.path.join(out, exe)], capture_output=True, text=True, env=env)
+        msgs = [ln for ln in r.stderr.splitlines() if ln.startswith("Failed to create VQ-VAE backend:")]
+        if embedded:
+            good = len(msgs) == 2 and (gpu or all("no HIP device available" in m for m in msgs)) and "no weight pack given" not in r.stderr
+        else:
+            good = len(msgs) == 2 and all("no weight pack given (embedded model absent from this build)" in m for m in msgs)
+        print(f"  SOP route [{name}]: {r.stdout.strip()} | {msgs[0] if msgs else r.stderr.strip()} -> {'ok' if good else 'FAILED'}")
+        ok = ok and good
+    print("integration proof: " + ("OK" if ok else "FAILED"))
+    return ok
+
+
+def main(argv) -> int:
+    if "--run" in argv:
+        return 0 if run_proofs(argv[argv.index("--run") + 1], gpu="--gpu" in argv) else 1
+    if not os.path.isdir(REF):
+        print(f"integration proof: SKIPPED (no reference checkout at {REF_ROOT}; set VQVDB_REFERENCE)")
+        return 0
+    if "--build" in argv:
+        return 0 if build_proofs(argv[argv.index("--build") + 1]) else 1
+    tmp = tempfile.mkdtemp(prefix="vqhip_integration_out_")
+    try:
+        return 0 if build_proofs(tmp) and run_proofs(tmp) else 1
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
 
 if __name__ == "__main__":
     sys.path.insert(0, ROOT)
-    sys.exit(main())
+    sys.exit(main(sys.argv[1:]))
