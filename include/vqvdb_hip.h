@@ -286,6 +286,43 @@ int vqhip_selftest_mfma(vqhip_codec* codec, int64_t mismatches[2]);
 
 const char* vqhip_version(void);
 
+/* ---- Vec3 model (extension) -----------------------------------------------------------------
+ * The reference's second model, VQVAE(3, 64, K) (python/VQVAE_v2.py EncoderVec3 / DecoderVec3, picked for every
+ * in_channels != 1), for OpenVDB Vec3f grids, on a handle of its own.  A Vec3 pack given to vqhip_create keeps failing
+ * and a scalar pack given to vqhip_vec3_create fails with "not a Vec3 model pack".
+ *   leaves  : float32 [n][512][3]  channels last: the byte layout of a Vec3f leaf buffer (voxel d*64 + h*8 + w, then x, y, z)
+ *   indices : uint16  [n][64]      position d*16 + h*4 + w; every index < num_codes
+ * Pack: VQWPACK1 with the 61 inference tensors of VQVAE(3, 64, K).state_dict() (training buffers optional, ignored);
+ * embedding_dim must be 64, num_codes K = rows of quantizer.embedding, 1 <= K <= 65536.  Status codes, error strings and
+ * the no-throw / no-abort and one-call-in-flight rules are those of vqhip_codec.  n_leaves == 0 does nothing and returns
+ * VQHIP_OK.  Results never depend on the batch size, the position of a leaf in the batch, the chunk size or the entry point.
+ * Decoder outputs are tanh values, |y| <= 1. */
+typedef struct vqhip_vec3_codec vqhip_vec3_codec;
+int vqhip_vec3_create(const char* pack_path, const void* pack_bytes, size_t pack_size, int device_id, vqhip_vec3_codec** out);
+void vqhip_vec3_destroy(vqhip_vec3_codec* codec);
+/* Message of the last failure on this handle (codec == NULL: last failure of vqhip_vec3_create on the calling thread). */
+const char* vqhip_vec3_last_error(const vqhip_vec3_codec* codec);
+/* num_codes = K, embedding_dim = 64, latent = {4,4,4}; any pointer may be NULL. */
+int vqhip_vec3_model_info(const vqhip_vec3_codec* codec, int64_t* num_codes, int64_t* embedding_dim, int64_t latent[3]);
+/* Host pointers.  decode checks every index against num_codes before it launches anything (VQHIP_ERR_INVALID). */
+int vqhip_vec3_encode(vqhip_vec3_codec* codec, const float* leaves, int64_t n_leaves, uint16_t* indices);
+int vqhip_vec3_decode(vqhip_vec3_codec* codec, const uint16_t* indices, int64_t n_leaves, float* leaves);
+/* Device pointers on the codec's device, enqueued on hip_stream (NULL = the codec's own), not synchronised on return.
+ * Precondition of decode_device: every index < num_codes.  It is not checked on the host; the gather clamps an index to
+ * num_codes - 1, so no index reads outside the codebook. */
+int vqhip_vec3_encode_device(vqhip_vec3_codec* codec, const float* leaves_dev, int64_t n_leaves, uint16_t* indices_dev, void* hip_stream);
+int vqhip_vec3_decode_device(vqhip_vec3_codec* codec, const uint16_t* indices_dev, int64_t n_leaves, float* leaves_dev, void* hip_stream);
+/* Leaves per internal pass (default 16384: 0.34 MB of workspace per leaf, about 5.6 GB).  Halved at the first call until
+ * workspace + I/O buffers fit into 80 % of the free device memory (never below 1024 leaves).  Accepted: 1 .. 131072. */
+int vqhip_vec3_set_chunk_leaves(vqhip_vec3_codec* codec, int64_t chunk_leaves);
+int64_t vqhip_vec3_chunk_leaves(const vqhip_vec3_codec* codec);
+/* Test hooks.  With debug on, every pass keeps copies of its intermediate activations; vqhip_vec3_debug_fetch copies
+ * those of the LAST chunk to host as float32 [n_leaves][C][positions] (NCDHW per leaf).  Names are the reference's module
+ * paths: encoder.pre.0 encoder.pre.2 encoder.pre encoder.down1 encoder.res_stack.0 encoder.res_stack.1 encoder.proj
+ * decoder.stem.0 decoder.stem decoder.res_stack.0 decoder.res_stack.1 decoder.up_conv. */
+int vqhip_vec3_debug_enable(vqhip_vec3_codec* codec, int enable);
+int vqhip_vec3_debug_fetch(vqhip_vec3_codec* codec, const char* name, int64_t n_leaves, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,9 @@ ABI_SYMBOLS = [
     "vqhip_fulltrain_begin", "vqhip_fulltrain_param_count", "vqhip_fulltrain_forward_device", "vqhip_fulltrain_fwdbwd_device",
     "vqhip_fulltrain_apply_device", "vqhip_fulltrain_get_params", "vqhip_fulltrain_set_params",
     "vqhip_fulltrain_get_opt_state", "vqhip_fulltrain_set_opt_state", "vqhip_workspace_bytes", "vqhip_chunk_leaves", "vqhip_multi_worker_info", "vqhip_fulltrain_fwdbwd_overlap_device", "vqhip_fulltrain_decoder_offset", "vqhip_fulltrain_ready_stream", "vqhip_fulltrain_set_folded_tail",
+    "vqhip_vec3_create", "vqhip_vec3_destroy", "vqhip_vec3_last_error", "vqhip_vec3_model_info", "vqhip_vec3_encode", "vqhip_vec3_decode",
+    "vqhip_vec3_encode_device", "vqhip_vec3_decode_device", "vqhip_vec3_set_chunk_leaves", "vqhip_vec3_chunk_leaves",
+    "vqhip_vec3_debug_enable", "vqhip_vec3_debug_fetch",
 ]
 
 class _GridInfo(ctypes.Structure):
@@ -195,15 +198,134 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_multi_decode.argtypes = [vp, vp, i64, vp]
     lib.vqhip_decompress_file.argtypes = [vp, ctypes.c_char_p, i64, GRID_BEGIN_FN, LEAF_ALLOC_FN, vp, ctypes.POINTER(StreamStats)]
     lib.vqhip_compress_file.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(_GridSource), ci, i64, ctypes.POINTER(StreamStats)]
+    lib.vqhip_vec3_create.argtypes = [ctypes.c_char_p, vp, ctypes.c_size_t, ci, ctypes.POINTER(vp)]
+    lib.vqhip_vec3_destroy.argtypes = [vp]
+    lib.vqhip_vec3_destroy.restype = None
+    lib.vqhip_vec3_last_error.argtypes = [vp]
+    lib.vqhip_vec3_last_error.restype = ctypes.c_char_p
+    lib.vqhip_vec3_model_info.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    lib.vqhip_vec3_encode.argtypes = [vp, vp, i64, vp]
+    lib.vqhip_vec3_decode.argtypes = [vp, vp, i64, vp]
+    lib.vqhip_vec3_encode_device.argtypes = [vp, vp, i64, vp, vp]
+    lib.vqhip_vec3_decode_device.argtypes = [vp, vp, i64, vp, vp]
+    lib.vqhip_vec3_set_chunk_leaves.argtypes = [vp, i64]
+    lib.vqhip_vec3_chunk_leaves.argtypes = [vp]
+    lib.vqhip_vec3_chunk_leaves.restype = i64
+    lib.vqhip_vec3_debug_enable.argtypes = [vp, ci]
+    lib.vqhip_vec3_debug_fetch.argtypes = [vp, ctypes.c_char_p, i64, vp]
     for name in ABI_SYMBOLS:
         if getattr(lib, name).argtypes is None and name not in ("vqhip_version",):
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
         if name not in ("vqhip_destroy", "vqhip_last_error", "vqhip_version", "vqhip_multi_destroy", "vqhip_multi_last_error",
                         "vqhip_fulltrain_param_count", "vqhip_workspace_bytes", "vqhip_chunk_leaves", "vqhip_fulltrain_decoder_offset",
-                        "vqhip_fulltrain_ready_stream"):
+                        "vqhip_fulltrain_ready_stream", "vqhip_vec3_destroy", "vqhip_vec3_last_error", "vqhip_vec3_chunk_leaves"):
             getattr(lib, name).restype = ci
     _lib = lib
     return lib
+
+
+VEC3_LEAF_SHAPE = (512, 3)
+# debug_fetch names of the Vec3 handle -> (channels, positions) of one leaf
+VEC3_DEBUG_LAYERS = {
+    "encoder.pre.0": (64, 512), "encoder.pre.2": (64, 512), "encoder.pre": (64, 512), "encoder.down1": (128, 64),
+    "encoder.res_stack.0": (128, 64), "encoder.res_stack.1": (128, 64), "encoder.proj": (64, 64),
+    "decoder.stem.0": (128, 64), "decoder.stem": (128, 64), "decoder.res_stack.0": (128, 64), "decoder.res_stack.1": (128, 64),
+    "decoder.up_conv": (256, 64),
+}
+
+
+class HipVec3Codec:
+    """Owner of a ``vqhip_vec3_codec*``: the Vec3 model VQVAE(3, 64, K) (leaves float32 [n,512,3] channels last,
+    indices uint16 [n,64]).  Arguments are checked here, before any C call."""
+
+    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0):
+        self._lib = load_library()
+        self._h = ctypes.c_void_p()
+        if isinstance(pack, (bytes, bytearray, memoryview)):
+            self._pack = bytes(pack)
+            rc = self._lib.vqhip_vec3_create(None, self._pack, len(self._pack), device_id, ctypes.byref(self._h))
+        else:
+            rc = self._lib.vqhip_vec3_create(os.fspath(pack).encode(), None, 0, device_id, ctypes.byref(self._h))
+        if rc != 0:
+            raise RuntimeError(self._lib.vqhip_vec3_last_error(None).decode())
+
+    def _check(self, rc: int):
+        if rc != 0:
+            raise RuntimeError(self._lib.vqhip_vec3_last_error(self._h).decode())
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.vqhip_vec3_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    __del__ = close
+
+    def model_info(self) -> dict:
+        k, d, lat = ctypes.c_int64(), ctypes.c_int64(), (ctypes.c_int64 * 3)()
+        self._check(self._lib.vqhip_vec3_model_info(self._h, ctypes.byref(k), ctypes.byref(d), lat))
+        return {"num_codes": k.value, "embedding_dim": d.value, "latent_shape": list(lat)}
+
+    @staticmethod
+    def check_leaves(leaves) -> np.ndarray:
+        """float32, C-contiguous, [n,512,3] or [n,8,8,8,3] -> [n,512,3] view."""
+        if not isinstance(leaves, np.ndarray) or leaves.dtype != np.float32:
+            raise TypeError("vec3 leaves must be a float32 numpy array")
+        if not leaves.flags.c_contiguous:
+            raise ValueError("vec3 leaves must be C-contiguous")
+        if leaves.ndim == 3 and leaves.shape[1:] == (512, 3):
+            return leaves
+        if leaves.ndim == 5 and leaves.shape[1:] == (8, 8, 8, 3):
+            return leaves.reshape(-1, 512, 3)
+        raise ValueError(f"vec3 leaves must have shape [n,512,3] or [n,8,8,8,3], got {list(leaves.shape)}")
+
+    @staticmethod
+    def check_indices(indices) -> np.ndarray:
+        """uint16, C-contiguous, [n,64] or [n,4,4,4] -> [n,64] view."""
+        if not isinstance(indices, np.ndarray) or indices.dtype != np.uint16:
+            raise TypeError("vec3 indices must be a uint16 numpy array")
+        if not indices.flags.c_contiguous:
+            raise ValueError("vec3 indices must be C-contiguous")
+        if indices.ndim == 2 and indices.shape[1] == 64:
+            return indices
+        if indices.ndim == 4 and indices.shape[1:] == (4, 4, 4):
+            return indices.reshape(-1, 64)
+        raise ValueError(f"vec3 indices must have shape [n,64] or [n,4,4,4], got {list(indices.shape)}")
+
+    def encode(self, leaves: np.ndarray) -> np.ndarray:
+        leaves = self.check_leaves(leaves)
+        idx = np.empty((leaves.shape[0], 64), dtype=np.uint16)
+        self._check(self._lib.vqhip_vec3_encode(self._h, leaves.ctypes.data, leaves.shape[0], idx.ctypes.data))
+        return idx
+
+    def decode(self, indices: np.ndarray) -> np.ndarray:
+        indices = self.check_indices(indices)
+        out = np.empty((indices.shape[0], 512, 3), dtype=np.float32)
+        self._check(self._lib.vqhip_vec3_decode(self._h, indices.ctypes.data, indices.shape[0], out.ctypes.data))
+        return out
+
+    def encode_device(self, leaves_ptr: int, n: int, idx_ptr: int, stream: int = 0):
+        self._check(self._lib.vqhip_vec3_encode_device(self._h, leaves_ptr, n, idx_ptr, stream or None))
+
+    def decode_device(self, idx_ptr: int, n: int, leaves_ptr: int, stream: int = 0):
+        self._check(self._lib.vqhip_vec3_decode_device(self._h, idx_ptr, n, leaves_ptr, stream or None))
+
+    def set_chunk_leaves(self, n: int):
+        self._check(self._lib.vqhip_vec3_set_chunk_leaves(self._h, n))
+
+    def chunk_leaves(self) -> int:
+        return int(self._lib.vqhip_vec3_chunk_leaves(self._h))
+
+    def debug_enable(self, on: bool = True):
+        self._check(self._lib.vqhip_vec3_debug_enable(self._h, 1 if on else 0))
+
+    def debug_fetch(self, name: str, n: int) -> np.ndarray:
+        """Activation ``name`` of the last chunk's first n leaves as float32 [n, C, positions]."""
+        if name not in VEC3_DEBUG_LAYERS:
+            raise KeyError(f"unknown vec3 layer {name!r}; one of {sorted(VEC3_DEBUG_LAYERS)}")
+        ch, npos = VEC3_DEBUG_LAYERS[name]
+        out = np.empty((n, ch, npos), dtype=np.float32)
+        self._check(self._lib.vqhip_vec3_debug_fetch(self._h, name.encode(), n, out.ctypes.data))
+        return out
 
 
 class HipCodec:

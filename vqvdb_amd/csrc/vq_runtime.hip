@@ -2737,3 +2737,4 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 }  // extern "C"
 
 #include "vq_train_full.inc"
+#include "vq_vec3.inc"
