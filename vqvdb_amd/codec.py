@@ -102,6 +102,12 @@ ABI_SYMBOLS = [
     "vqhip_vec3_debug_enable", "vqhip_vec3_debug_fetch",
 ]
 
+# every symbol include/vqvdb_hip_vec3_train.h declares (Vec3 codebook training; kept apart from ABI_SYMBOLS)
+VEC3_TRAIN_SYMBOLS = [
+    "vqhip_vec3_train_stats_floats", "vqhip_vec3_train_begin", "vqhip_vec3_train_vq_stats_device", "vqhip_vec3_train_eval_device",
+    "vqhip_vec3_train_vq_update_device", "vqhip_vec3_train_get_state", "vqhip_vec3_train_set_state",
+]
+
 class _GridInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("transform", ctypes.c_float * 16), ("latent_shape", ctypes.c_int64 * 3),
                 ("num_embeddings", ctypes.c_uint32), ("total_blocks", ctypes.c_uint64), ("grid_index", ctypes.c_int)]
@@ -213,6 +219,20 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_chunk_leaves.restype = i64
     lib.vqhip_vec3_debug_enable.argtypes = [vp, ci]
     lib.vqhip_vec3_debug_fetch.argtypes = [vp, ctypes.c_char_p, i64, vp]
+    # include/vqvdb_hip_vec3_train.h
+    lib.vqhip_vec3_train_stats_floats.argtypes = [vp]
+    lib.vqhip_vec3_train_stats_floats.restype = i64
+    lib.vqhip_vec3_train_begin.argtypes = [vp, vp, vp]
+    lib.vqhip_vec3_train_vq_stats_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.vqhip_vec3_train_eval_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.vqhip_vec3_train_vq_update_device.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp]
+    lib.vqhip_vec3_train_get_state.argtypes = [vp, vp, vp, vp]
+    lib.vqhip_vec3_train_set_state.argtypes = [vp, vp, vp, vp]
+    for name in VEC3_TRAIN_SYMBOLS:
+        if getattr(lib, name).argtypes is None:
+            raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
+        if name != "vqhip_vec3_train_stats_floats":
+            getattr(lib, name).restype = ci
     for name in ABI_SYMBOLS:
         if getattr(lib, name).argtypes is None and name not in ("vqhip_version",):
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -326,6 +346,67 @@ class HipVec3Codec:
         out = np.empty((n, ch, npos), dtype=np.float32)
         self._check(self._lib.vqhip_vec3_debug_fetch(self._h, name.encode(), n, out.ctypes.data))
         return out
+
+    # ---- codebook (EMA) training: include/vqvdb_hip_vec3_train.h ----
+    @staticmethod
+    def check_train_batch(n: int, stats_ptr: int):
+        if not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError(f"n must be a non-negative leaf count, got {n!r}")
+        if not stats_ptr:
+            raise ValueError("stats_ptr is NULL: the statistics need a device buffer of train_stats_floats() float32")
+
+    @staticmethod
+    def check_ema(decay: float, eps: float):
+        if not (0.0 <= decay <= 1.0):
+            raise ValueError(f"decay must be in [0, 1], got {decay}")
+        if not eps > 0.0:
+            raise ValueError(f"eps must be > 0, got {eps}")
+
+    @staticmethod
+    def check_state(k_codes: int, embedding=None, cluster_size=None, embed_avg=None) -> list:
+        """float32 C-contiguous copies of the given buffers (None stays None), sizes K*64 / K / K*64."""
+        out = []
+        for a, size, what in zip((embedding, cluster_size, embed_avg), (k_codes * 64, k_codes, k_codes * 64),
+                                 ("embedding", "cluster_size", "embed_avg")):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != size:
+                    raise ValueError(f"{what}: expected {size} float32 values, got {a.size}")
+            out.append(a)
+        return out
+
+    def train_stats_floats(self) -> int:
+        return int(self._lib.vqhip_vec3_train_stats_floats(self._h))
+
+    def train_begin(self, cluster_size=None, embed_avg=None):
+        _, cs, av = self.check_state(self.model_info()["num_codes"], None, cluster_size, embed_avg)
+        self._check(self._lib.vqhip_vec3_train_begin(self._h, None if cs is None else cs.ctypes.data, None if av is None else av.ctypes.data))
+
+    def train_vq_stats_device(self, leaves_ptr: int, n: int, stats_ptr: int, idx_ptr: int = 0, latent_ptr: int = 0, stream: int = 0):
+        self.check_train_batch(n, stats_ptr)
+        self._check(self._lib.vqhip_vec3_train_vq_stats_device(self._h, leaves_ptr, n, stats_ptr, idx_ptr or None, latent_ptr or None, stream or None))
+
+    def train_eval_device(self, leaves_ptr: int, n: int, stats_ptr: int, recon_sums_ptr: int, recon_ptr: int = 0, stream: int = 0):
+        self.check_train_batch(n, stats_ptr)
+        if not recon_sums_ptr:
+            raise ValueError("recon_sums_ptr is NULL: the reconstruction sums need a device buffer of 3 float32")
+        self._check(self._lib.vqhip_vec3_train_eval_device(self._h, leaves_ptr, n, stats_ptr, recon_sums_ptr, recon_ptr or None, stream or None))
+
+    def train_vq_update_device(self, stats_ptr: int, decay: float = 0.95, eps: float = 1e-4, stream: int = 0):
+        self.check_ema(decay, eps)
+        if not stats_ptr:
+            raise ValueError("stats_ptr is NULL")
+        self._check(self._lib.vqhip_vec3_train_vq_update_device(self._h, stats_ptr, decay, eps, stream or None))
+
+    def train_get_state(self) -> dict:
+        k = self.model_info()["num_codes"]
+        emb, cs, avg = np.empty((k, 64), np.float32), np.empty(k, np.float32), np.empty((k, 64), np.float32)
+        self._check(self._lib.vqhip_vec3_train_get_state(self._h, emb.ctypes.data, cs.ctypes.data, avg.ctypes.data))
+        return {"embedding": emb, "cluster_size": cs, "embed_avg": avg}
+
+    def train_set_state(self, embedding=None, cluster_size=None, embed_avg=None):
+        arrs = self.check_state(self.model_info()["num_codes"], embedding, cluster_size, embed_avg)
+        self._check(self._lib.vqhip_vec3_train_set_state(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
 
 
 class HipCodec:

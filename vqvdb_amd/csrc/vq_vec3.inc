@@ -2,6 +2,7 @@
 // translation unit: it reuses the weight-pack parser (parse_pack / need) and nothing else of the scalar handle.
 
 #include "vq_vec3.h"
+#include "vq_vec3_train.h"
 
 struct vqhip_vec3_codec {
     int device = 0;
@@ -17,6 +18,12 @@ struct vqhip_vec3_codec {
     uint16_t* io_idx = nullptr;        // [chunk][64]
     int64_t io_n = 0;
     bool debug = false;
+    // codebook training (vq_vec3_train.inc): set by vqhip_vec3_train_begin
+    bool training = false;
+    float* tr_cs = nullptr;            // cluster_size [K]
+    float* tr_avg = nullptr;           // embed_avg [K][64]
+    unsigned char* tr_ws = nullptr;    // training workspace of tr_leaves leaves (v3t_ws_bytes)
+    int64_t tr_leaves = 0;
     struct Dbg {
         float* p = nullptr;
         int64_t cap = 0, n = 0;
@@ -288,13 +295,19 @@ int v3_ensure_ws(vqhip_vec3_codec* c, int64_t m)
     return VQHIP_OK;
 }
 
-// halve the chunk until workspace + I/O slots fit into 80 % of the free device memory (never below 1024 leaves)
+size_t v3t_ws_bytes(int64_t leaves, int k_codes);   // vq_vec3_train.inc: training workspace of a chunk (0 for 0 leaves)
+
+// halve the chunk until workspace + I/O slots (+ the training workspace once training has begun) fit into 80 % of the free device memory (never below 1024 leaves)
 void v3_fit_chunk(vqhip_vec3_codec* c)
 {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;
     free_b += (size_t)c->ws_leaves * V3_LEAF_FLOATS * sizeof(float) + (size_t)c->io_n * V3_IO_BYTES;
-    while (c->chunk > 1024 && (size_t)c->chunk * (V3_LEAF_FLOATS * sizeof(float) + V3_IO_BYTES) > free_b / 5 * 4)
+    if (c->training) free_b += v3t_ws_bytes(c->tr_leaves, c->k_codes);
+    auto need = [&](int64_t m) {
+        return (size_t)m * (V3_LEAF_FLOATS * sizeof(float) + V3_IO_BYTES) + (c->training ? v3t_ws_bytes(m, c->k_codes) : 0);
+    };
+    while (c->chunk > 1024 && need(c->chunk) > free_b / 5 * 4)
         c->chunk = (c->chunk / 2 + 31) / 32 * 32;
     c->chunk_fitted = true;
 }
@@ -392,14 +405,13 @@ int v3_encode_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_
     return v3_launch_check(c, "vec3 quantizer");
 }
 
-int v3_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s)
+// the decoder from decoder.stem on, reading its input [m][64][64] from W.z (workspace of at least m leaves)
+int v3_decode_from_z(vqhip_vec3_codec* c, int64_t m, float* out, hipStream_t s)
 {
-    if (int rc = v3_ensure_ws(c, m)) return rc;
     const V3Ws W = v3_ws(c);
     auto& w = c->w;
     const unsigned nb = (unsigned)m;
     int rc = VQHIP_OK;
-    hipLaunchKernelGGL(v3::gather_k, dim3(v3_ew_grid(m * 4096)), dim3(256), 0, s, idx, w["cb"], c->k_codes, W.z, m);
     v3_conv(v3_stem, L_stem{}, s, m, v3_args(W.z, w["d.stem.wf"], w["d.stem.b"], W.p), 2);
     if ((rc = v3_launch_check(c, "vec3 decoder.stem.0")) || (rc = v3_keep(c, "decoder.stem.0", W.p, 128 * 64, m, s))) return rc;
     hipLaunchKernelGGL((v3::gn_stats_k<128, 64>), dim3(nb), dim3(256), 0, s, W.p, W.stats, m);
@@ -415,6 +427,13 @@ int v3_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* 
     if ((rc = v3_launch_check(c, "vec3 decoder.up_conv")) || (rc = v3_keep(c, "decoder.up_conv", W.u, 256 * 64, m, s))) return rc;
     hipLaunchKernelGGL(v3::final_k, dim3(nb), dim3(512), V3_LDS_FINAL, s, W.u, w["d.final.w"], w["d.final.b"], out, m);
     return v3_launch_check(c, "vec3 decoder.final");
+}
+
+int v3_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s)
+{
+    if (int rc = v3_ensure_ws(c, m)) return rc;
+    hipLaunchKernelGGL(v3::gather_k, dim3(v3_ew_grid(m * 4096)), dim3(256), 0, s, idx, c->w["cb"], c->k_codes, v3_ws(c).z, m);
+    return v3_decode_from_z(c, m, out, s);
 }
 
 int v3_ensure_io(vqhip_vec3_codec* c, int64_t m)
@@ -506,6 +525,9 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     if (c->ws) hipFree(c->ws);
     if (c->io_leaves) hipFree(c->io_leaves);
     if (c->io_idx) hipFree(c->io_idx);
+    if (c->tr_cs) hipFree(c->tr_cs);
+    if (c->tr_avg) hipFree(c->tr_avg);
+    if (c->tr_ws) hipFree(c->tr_ws);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
