@@ -108,6 +108,16 @@ VEC3_TRAIN_SYMBOLS = [
     "vqhip_vec3_train_vq_update_device", "vqhip_vec3_train_get_state", "vqhip_vec3_train_set_state",
 ]
 
+# every symbol include/vqvdb_hip_vec3_fulltrain.h declares (Vec3 full training; kept apart from both lists above)
+VEC3_FULLTRAIN_SYMBOLS = [
+    "vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats",
+    "vqhip_vec3_fulltrain_begin", "vqhip_vec3_fulltrain_fwdbwd_device", "vqhip_vec3_fulltrain_forward_device",
+    "vqhip_vec3_fulltrain_apply_device", "vqhip_vec3_fulltrain_get_params", "vqhip_vec3_fulltrain_set_params",
+    "vqhip_vec3_fulltrain_get_opt_state", "vqhip_vec3_fulltrain_set_opt_state",
+]
+_VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
+
+
 class _GridInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char_p), ("transform", ctypes.c_float * 16), ("latent_shape", ctypes.c_int64 * 3),
                 ("num_embeddings", ctypes.c_uint32), ("total_blocks", ctypes.c_uint64), ("grid_index", ctypes.c_int)]
@@ -228,6 +238,23 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_train_vq_update_device.argtypes = [vp, vp, ctypes.c_float, ctypes.c_float, vp]
     lib.vqhip_vec3_train_get_state.argtypes = [vp, vp, vp, vp]
     lib.vqhip_vec3_train_set_state.argtypes = [vp, vp, vp, vp]
+    # include/vqvdb_hip_vec3_fulltrain.h
+    for name in _VEC3_FULLTRAIN_I64:
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = i64
+    lib.vqhip_vec3_fulltrain_begin.argtypes = [vp]
+    lib.vqhip_vec3_fulltrain_fwdbwd_device.argtypes = [vp, vp, i64, i64, vp, vp, vp, vp]
+    lib.vqhip_vec3_fulltrain_forward_device.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.vqhip_vec3_fulltrain_apply_device.argtypes = [vp, vp, vp, cf, i64, cf, cf, cf, cf, cf, cf, vp]
+    lib.vqhip_vec3_fulltrain_get_params.argtypes = [vp, vp]
+    lib.vqhip_vec3_fulltrain_set_params.argtypes = [vp, vp]
+    lib.vqhip_vec3_fulltrain_get_opt_state.argtypes = [vp, vp, vp]
+    lib.vqhip_vec3_fulltrain_set_opt_state.argtypes = [vp, vp, vp]
+    for name in VEC3_FULLTRAIN_SYMBOLS:
+        if getattr(lib, name).argtypes is None:
+            raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
+        if name not in _VEC3_FULLTRAIN_I64:
+            getattr(lib, name).restype = ci
     for name in VEC3_TRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -407,6 +434,87 @@ class HipVec3Codec:
     def train_set_state(self, embedding=None, cluster_size=None, embed_avg=None):
         arrs = self.check_state(self.model_info()["num_codes"], embedding, cluster_size, embed_avg)
         self._check(self._lib.vqhip_vec3_train_set_state(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----
+    @staticmethod
+    def check_fulltrain_batch(n: int, n_global: int, grads_ptr: int, aux_ptr: int):
+        if not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError(f"n must be a non-negative leaf count, got {n!r}")
+        if not isinstance(n_global, (int, np.integer)) or n_global < max(n, 1):
+            raise ValueError(f"n_global must be >= n and >= 1, got n_global={n_global!r}, n={n}")
+        if not grads_ptr:
+            raise ValueError("grads_ptr is NULL: the gradients need a device buffer of fulltrain_param_count() float32")
+        if not aux_ptr:
+            raise ValueError("aux_ptr is NULL: the statistics need a device buffer of fulltrain_aux_floats() float32")
+
+    @staticmethod
+    def check_adamw(lr: float, step: int, betas, adam_eps: float, weight_decay: float):
+        if not isinstance(step, (int, np.integer)) or step < 1:
+            raise ValueError(f"step must be an integer >= 1, got {step!r}")
+        if not lr >= 0.0:
+            raise ValueError(f"lr must be >= 0, got {lr}")
+        if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"betas must be two values in [0, 1), got {betas}")
+        if not adam_eps > 0.0:
+            raise ValueError(f"adam_eps must be > 0, got {adam_eps}")
+        if not weight_decay >= 0.0:
+            raise ValueError(f"weight_decay must be >= 0, got {weight_decay}")
+
+    def _check_vector(self, a, what: str) -> np.ndarray:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size != self.fulltrain_param_count():
+            raise ValueError(f"{what}: expected {self.fulltrain_param_count()} float32 values, got {a.size}")
+        return a
+
+    def fulltrain_param_count(self) -> int:
+        return int(self._lib.vqhip_vec3_fulltrain_param_count(self._h))
+
+    def fulltrain_decoder_offset(self) -> int:
+        return int(self._lib.vqhip_vec3_fulltrain_decoder_offset(self._h))
+
+    def fulltrain_aux_floats(self) -> int:
+        return int(self._lib.vqhip_vec3_fulltrain_aux_floats(self._h))
+
+    def fulltrain_begin(self):
+        self._check(self._lib.vqhip_vec3_fulltrain_begin(self._h))
+
+    def fulltrain_fwdbwd_device(self, leaves_ptr: int, n: int, n_global: int, grads_ptr: int, aux_ptr: int, latent_ptr: int = 0, stream: int = 0):
+        self.check_fulltrain_batch(n, n_global, grads_ptr, aux_ptr)
+        self._check(self._lib.vqhip_vec3_fulltrain_fwdbwd_device(self._h, leaves_ptr, n, n_global, grads_ptr, aux_ptr, latent_ptr or None,
+                                                                 stream or None))
+
+    def fulltrain_forward_device(self, leaves_ptr: int, n: int, idx_ptr: int = 0, recon_ptr: int = 0, stream: int = 0):
+        if not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError(f"n must be a non-negative leaf count, got {n!r}")
+        self._check(self._lib.vqhip_vec3_fulltrain_forward_device(self._h, leaves_ptr, n, idx_ptr or None, recon_ptr or None, stream or None))
+
+    def fulltrain_apply_device(self, grads_ptr: int, aux_ptr: int, lr: float, step: int, betas=(0.9, 0.999), adam_eps: float = 1e-8,
+                               weight_decay: float = 1e-4, decay: float = 0.95, eps: float = 1e-4, stream: int = 0):
+        if not grads_ptr:
+            raise ValueError("grads_ptr is NULL")
+        self.check_adamw(lr, step, betas, adam_eps, weight_decay)
+        if aux_ptr:
+            self.check_ema(decay, eps)
+        self._check(self._lib.vqhip_vec3_fulltrain_apply_device(self._h, grads_ptr, aux_ptr or None, lr, step, betas[0], betas[1], adam_eps,
+                                                                weight_decay, decay, eps, stream or None))
+
+    def fulltrain_get_params(self) -> np.ndarray:
+        out = np.empty(self.fulltrain_param_count(), np.float32)
+        self._check(self._lib.vqhip_vec3_fulltrain_get_params(self._h, out.ctypes.data))
+        return out
+
+    def fulltrain_set_params(self, params):
+        p = self._check_vector(params, "params")
+        self._check(self._lib.vqhip_vec3_fulltrain_set_params(self._h, p.ctypes.data))
+
+    def fulltrain_get_opt_state(self) -> tuple:
+        m, v = np.empty(self.fulltrain_param_count(), np.float32), np.empty(self.fulltrain_param_count(), np.float32)
+        self._check(self._lib.vqhip_vec3_fulltrain_get_opt_state(self._h, m.ctypes.data, v.ctypes.data))
+        return m, v
+
+    def fulltrain_set_opt_state(self, exp_avg, exp_avg_sq):
+        m, v = self._check_vector(exp_avg, "exp_avg"), self._check_vector(exp_avg_sq, "exp_avg_sq")
+        self._check(self._lib.vqhip_vec3_fulltrain_set_opt_state(self._h, m.ctypes.data, v.ctypes.data))
 
 
 class HipCodec:

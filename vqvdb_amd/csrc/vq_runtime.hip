@@ -2739,3 +2739,4 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_train_full.inc"
 #include "vq_vec3.inc"
 #include "vq_vec3_train.inc"
+#include "vq_vec3_fulltrain.inc"

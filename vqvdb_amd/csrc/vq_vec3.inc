@@ -24,6 +24,11 @@ struct vqhip_vec3_codec {
     float* tr_avg = nullptr;           // embed_avg [K][64]
     unsigned char* tr_ws = nullptr;    // training workspace of tr_leaves leaves (v3t_ws_bytes)
     int64_t tr_leaves = 0;
+    // full training (vq_vec3_fulltrain.inc): set by vqhip_vec3_fulltrain_begin; P, M, V live in w ("ft.P", "ft.M", "ft.V")
+    bool ft_on = false;
+    float *ft_P = nullptr, *ft_M = nullptr, *ft_V = nullptr;
+    float* ft_ws = nullptr;            // activations, gradients and partials of ft_leaves leaves (v3f_ws_bytes)
+    int64_t ft_leaves = 0;
     struct Dbg {
         float* p = nullptr;
         int64_t cap = 0, n = 0;
@@ -296,16 +301,19 @@ int v3_ensure_ws(vqhip_vec3_codec* c, int64_t m)
 }
 
 size_t v3t_ws_bytes(int64_t leaves, int k_codes);   // vq_vec3_train.inc: training workspace of a chunk (0 for 0 leaves)
+size_t v3f_ws_bytes(int64_t leaves);                // vq_vec3_fulltrain.inc: full-training workspace of a chunk (0 for 0 leaves)
 
-// halve the chunk until workspace + I/O slots (+ the training workspace once training has begun) fit into 80 % of the free device memory (never below 1024 leaves)
+// halve the chunk until workspace + I/O slots (+ the training workspaces once training has begun) fit into 80 % of the free device memory (never below 1024 leaves)
 void v3_fit_chunk(vqhip_vec3_codec* c)
 {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;
     free_b += (size_t)c->ws_leaves * V3_LEAF_FLOATS * sizeof(float) + (size_t)c->io_n * V3_IO_BYTES;
     if (c->training) free_b += v3t_ws_bytes(c->tr_leaves, c->k_codes);
+    if (c->ft_on) free_b += v3f_ws_bytes(c->ft_leaves);
     auto need = [&](int64_t m) {
-        return (size_t)m * (V3_LEAF_FLOATS * sizeof(float) + V3_IO_BYTES) + (c->training ? v3t_ws_bytes(m, c->k_codes) : 0);
+        return (size_t)m * (V3_LEAF_FLOATS * sizeof(float) + V3_IO_BYTES) + (c->training ? v3t_ws_bytes(m, c->k_codes) : 0) +
+               (c->ft_on ? v3f_ws_bytes(m) : 0);
     };
     while (c->chunk > 1024 && need(c->chunk) > free_b / 5 * 4)
         c->chunk = (c->chunk / 2 + 31) / 32 * 32;
@@ -528,6 +536,7 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     if (c->tr_cs) hipFree(c->tr_cs);
     if (c->tr_avg) hipFree(c->tr_avg);
     if (c->tr_ws) hipFree(c->tr_ws);
+    if (c->ft_ws) hipFree(c->ft_ws);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
