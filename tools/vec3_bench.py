@@ -5,7 +5,10 @@ timed with device events after a warm-up, at 16 384 and 65 536 leaves.  Prints o
 FLOPs per leaf are counted here from the layer shapes, taps inside the leaf only (zero padding skipped, as the kernels do),
 2 FLOPs per multiply-add; the fraction of peak is against 155 TFLOP/s, the measured fp32-MFMA rate of the MI355X.
 
-    python tools/vec3_bench.py [--sizes 16384,65536] [--reps 5] [--out profiles/vec3_bench.json]
+    python tools/vec3_bench.py [--sizes 16384,65536] [--reps 5] [--precision fp32|bf16|both] [--out profiles/vec3_bench.json]
+
+--precision bf16 / both adds the bf16-operand inference mode on the same handle, under "bf16" per size; its
+fraction of peak is still against the fp32-MFMA rate, so that the two modes' columns compare directly.
 """
 import argparse
 import json
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--sizes", default="16384,65536")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--precision", choices=("fp32", "bf16", "both"), default="fp32")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
@@ -60,8 +64,11 @@ def main():
         out = torch.empty((n, 512, 3), dtype=torch.float32, device="cuda")
         torch.cuda.synchronize()
         row = {}
-        for name, fn, flop in (("encode", lambda: c.encode_device(leaves.data_ptr(), n, idx.data_ptr(), st.cuda_stream), fe),
-                               ("decode", lambda: c.decode_device(idx.data_ptr(), n, out.data_ptr(), st.cuda_stream), fd)):
+        modes = {"fp32": ("fp32",), "bf16": ("bf16",), "both": ("fp32", "bf16")}[a.precision]
+        for mode, name, fn, flop in [(m, *t) for m in modes for t in (
+                ("encode", lambda: c.encode_device(leaves.data_ptr(), n, idx.data_ptr(), st.cuda_stream), fe),
+                ("decode", lambda: c.decode_device(idx.data_ptr(), n, out.data_ptr(), st.cuda_stream), fd))]:
+            c.precision = mode
             for _ in range(a.warmup):
                 fn()
             torch.cuda.synchronize()
@@ -74,7 +81,8 @@ def main():
                 torch.cuda.synchronize()
                 times.append(s.elapsed_time(e) / 1e3)
             t = float(np.median(times))
-            row[name] = {"median_s": t, "min_s": float(min(times)), "leaves_per_s": n / t,
+            dst = row if mode == "fp32" else row.setdefault("bf16", {})
+            dst[name] = {"median_s": t, "min_s": float(min(times)), "leaves_per_s": n / t,
                          "tflops": flop * n / t / 1e12, "frac_of_peak": flop * n / t / 1e12 / PEAK_TFLOPS}
         res["sizes"][str(n)] = row
     c.close()

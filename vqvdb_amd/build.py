@@ -15,7 +15,8 @@ SRC = os.path.join(HERE, "csrc", "vq_runtime.hip")
 # every file of csrc/ is part of the one translation unit (vq_runtime.hip includes the kernel headers and vq_train_full.inc)
 DEPS = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".h", ".inc"))) + [
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip.h"), os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_train.h"),
-    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_fulltrain.h")]
+    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_fulltrain.h"),
+    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_precision.h")]
 LIB = os.path.join(HERE, "libvqvdb_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wno-unused-value", "-Wno-unused-result"]

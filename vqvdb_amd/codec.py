@@ -115,6 +115,10 @@ VEC3_FULLTRAIN_SYMBOLS = [
     "vqhip_vec3_fulltrain_apply_device", "vqhip_vec3_fulltrain_get_params", "vqhip_vec3_fulltrain_set_params",
     "vqhip_vec3_fulltrain_get_opt_state", "vqhip_vec3_fulltrain_set_opt_state",
 ]
+# every symbol include/vqvdb_hip_vec3_precision.h declares (Vec3 inference precision mode; kept apart from the lists above)
+VEC3_PRECISION_SYMBOLS = ["vqhip_vec3_set_precision", "vqhip_vec3_get_precision"]
+VEC3_PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_VEC3_PRECISION_*
+
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
 
 
@@ -250,6 +254,11 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_fulltrain_set_params.argtypes = [vp, vp]
     lib.vqhip_vec3_fulltrain_get_opt_state.argtypes = [vp, vp, vp]
     lib.vqhip_vec3_fulltrain_set_opt_state.argtypes = [vp, vp, vp]
+    # include/vqvdb_hip_vec3_precision.h
+    lib.vqhip_vec3_set_precision.argtypes = [vp, ci]
+    lib.vqhip_vec3_get_precision.argtypes = [vp, vp]
+    for name in VEC3_PRECISION_SYMBOLS:
+        getattr(lib, name).restype = ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -285,7 +294,8 @@ class HipVec3Codec:
     """Owner of a ``vqhip_vec3_codec*``: the Vec3 model VQVAE(3, 64, K) (leaves float32 [n,512,3] channels last,
     indices uint16 [n,64]).  Arguments are checked here, before any C call."""
 
-    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0):
+    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0, precision: str = "fp32"):
+        self.check_precision(precision)
         self._lib = load_library()
         self._h = ctypes.c_void_p()
         if isinstance(pack, (bytes, bytearray, memoryview)):
@@ -295,6 +305,26 @@ class HipVec3Codec:
             rc = self._lib.vqhip_vec3_create(os.fspath(pack).encode(), None, 0, device_id, ctypes.byref(self._h))
         if rc != 0:
             raise RuntimeError(self._lib.vqhip_vec3_last_error(None).decode())
+        if precision != "fp32":
+            self.precision = precision
+
+    @staticmethod
+    def check_precision(precision) -> int:
+        """"fp32" / "bf16" -> VQHIP_VEC3_PRECISION_* (include/vqvdb_hip_vec3_precision.h)."""
+        if precision not in VEC3_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(VEC3_PRECISIONS)}, got {precision!r}")
+        return VEC3_PRECISIONS[precision]
+
+    @property
+    def precision(self) -> str:
+        """Operand precision of the convolutions of encode / decode / debug_fetch: "fp32" (default) or "bf16" (DESIGN §14)."""
+        mode = ctypes.c_int(-1)
+        self._check(self._lib.vqhip_vec3_get_precision(self._h, ctypes.byref(mode)))
+        return {v: k for k, v in VEC3_PRECISIONS.items()}[mode.value]
+
+    @precision.setter
+    def precision(self, precision: str):
+        self._check(self._lib.vqhip_vec3_set_precision(self._h, self.check_precision(precision)))
 
     def _check(self, rc: int):
         if rc != 0:

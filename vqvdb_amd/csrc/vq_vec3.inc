@@ -18,6 +18,9 @@ struct vqhip_vec3_codec {
     uint16_t* io_idx = nullptr;        // [chunk][64]
     int64_t io_n = 0;
     bool debug = false;
+    // bf16-operand inference mode (vq_vec3_bf16.inc): VQHIP_VEC3_PRECISION_*; the bf16 fragment tables exist once bf_ready
+    int precision = 0;
+    bool bf_ready = false;
     // codebook training (vq_vec3_train.inc): set by vqhip_vec3_train_begin
     bool training = false;
     float* tr_cs = nullptr;            // cluster_size [K]
@@ -444,6 +447,21 @@ int v3_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* 
     return v3_decode_from_z(c, m, out, s);
 }
 
+// vq_vec3_bf16.inc: the same chunks with bf16 convolution operands
+int v3b_encode_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_t* idx, hipStream_t s);
+int v3b_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s);
+
+// the public entry points follow the handle's precision mode (training calls v3_encode_chunk / v3_decode_from_z: always fp32)
+int v3_encode_mode(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_t* idx, hipStream_t s)
+{
+    return c->precision ? v3b_encode_chunk(c, leaves, m, idx, s) : v3_encode_chunk(c, leaves, m, idx, s);
+}
+
+int v3_decode_mode(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s)
+{
+    return c->precision ? v3b_decode_chunk(c, idx, m, out, s) : v3_decode_chunk(c, idx, m, out, s);
+}
+
 int v3_ensure_io(vqhip_vec3_codec* c, int64_t m)
 {
     if (m <= c->io_n) return VQHIP_OK;
@@ -571,7 +589,7 @@ int vqhip_vec3_encode_device(vqhip_vec3_codec* c, const float* d_leaves, int64_t
     if (int rc = v3_prepare(c)) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int64_t o = 0; o < n; o += c->chunk)
-        if (int rc = v3_encode_chunk(c, d_leaves + o * 1536, std::min(c->chunk, n - o), d_idx + o * 64, s)) return rc;
+        if (int rc = v3_encode_mode(c, d_leaves + o * 1536, std::min(c->chunk, n - o), d_idx + o * 64, s)) return rc;
     return VQHIP_OK;
 }
 
@@ -584,7 +602,7 @@ int vqhip_vec3_decode_device(vqhip_vec3_codec* c, const uint16_t* d_idx, int64_t
     if (int rc = v3_prepare(c)) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int64_t o = 0; o < n; o += c->chunk)
-        if (int rc = v3_decode_chunk(c, d_idx + o * 64, std::min(c->chunk, n - o), d_out + o * 1536, s)) return rc;
+        if (int rc = v3_decode_mode(c, d_idx + o * 64, std::min(c->chunk, n - o), d_out + o * 1536, s)) return rc;
     return VQHIP_OK;
 }
 
@@ -599,7 +617,7 @@ int vqhip_vec3_encode(vqhip_vec3_codec* c, const float* leaves, int64_t n, uint1
         const int64_t m = std::min(c->chunk, n - o);
         if (int rc = v3_ensure_io(c, m)) return rc;
         HIPCHK(c, hipMemcpyAsync(c->io_leaves, leaves + o * 1536, (size_t)m * 1536 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (int rc = v3_encode_chunk(c, c->io_leaves, m, c->io_idx, c->stream)) return rc;
+        if (int rc = v3_encode_mode(c, c->io_leaves, m, c->io_idx, c->stream)) return rc;
         HIPCHK(c, hipMemcpyAsync(indices + o * 64, c->io_idx, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -621,7 +639,7 @@ int vqhip_vec3_decode(vqhip_vec3_codec* c, const uint16_t* indices, int64_t n, f
         const int64_t m = std::min(c->chunk, n - o);
         if (int rc = v3_ensure_io(c, m)) return rc;
         HIPCHK(c, hipMemcpyAsync(c->io_idx, indices + o * 64, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-        if (int rc = v3_decode_chunk(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
+        if (int rc = v3_decode_mode(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
         HIPCHK(c, hipMemcpyAsync(leaves + o * 1536, c->io_leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }

@@ -208,6 +208,8 @@ int v3f_rebuild(vqhip_vec3_codec* c, hipStream_t s)
         const V3FTensor& t = v3f_tensors().at(r.second);
         HIPCHK(c, hipMemcpyAsync(w[r.first], P + t.off, (size_t)t.size * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
+    if (c->bf_ready)   // bf16 inference mode: its fragments follow the fp32 ones just rebuilt
+        if (int rc = v3b_refrag(c, s)) return rc;
     return v3_launch_check(c, "vec3 full training: weight tables");
 }
 

@@ -209,6 +209,22 @@ def export_pack(pack_path: str, state: dict, out_path: str):
     weightpack.save(out_path, t)
 
 
+def eval_roundtrip(codec, leaves: torch.Tensor) -> dict:
+    """decode(encode(leaves)) of this rank's batch in the handle's current precision mode: reconstruction MSE and L1."""
+    leaves = leaves.contiguous()
+    n = leaves.shape[0]
+    idx = torch.empty((n, 64), dtype=torch.int16, device=leaves.device)
+    out = torch.empty((n, 512, 3), dtype=torch.float32, device=leaves.device)
+    st = torch.cuda.current_stream(leaves.device)
+    if st.cuda_stream == 0:   # a null handle means the codec's own stream: order it after the producer of `leaves` by hand
+        torch.cuda.synchronize(leaves.device)
+    codec.encode_device(leaves.data_ptr(), n, idx.data_ptr(), st.cuda_stream)
+    codec.decode_device(idx.data_ptr(), n, out.data_ptr(), st.cuda_stream)
+    torch.cuda.synchronize(leaves.device)
+    d = out - leaves.reshape(n, 512, 3)
+    return {"recon_mse": float((d * d).mean()), "recon_l1": float(d.abs().mean())}
+
+
 # ---- epoch driver ------------------------------------------------------------------------------------------------------
 def train(args) -> dict:
     from vqvdb_amd.sharding import shard_range
@@ -275,9 +291,21 @@ def train(args) -> dict:
             for k in val:
                 val[k] += mv[k] / n_val
         val_loss = val["recon_error"] + val["vq_loss"]
+        if args.eval_precision == "bf16":   # the same validation batches through encode / decode in bf16-operand mode
+            vb = {"recon_mse": 0.0, "recon_l1": 0.0}
+            codec.precision = "bf16"
+            for step in range(n_val):
+                ids = shard(va_ids, step) if len(va_ids) >= gb else va_ids[rank::world]
+                for k, v in eval_roundtrip(codec, d_all[torch.from_numpy(ids).to(device)]).items():
+                    vb[k] += v / n_val
+            codec.precision = "fp32"
+            vb["recon_error"] = 0.8 * vb["recon_mse"] + 0.2 * vb["recon_l1"]
         rec = {"epoch": epoch + 1, "train_loss": total / steps_per_epoch, "train_vq_loss": last["vq_loss"], "perplexity": last["perplexity"],
                "codes_used": last["codes_used"], "val_loss": val_loss, **{f"val_{k}": v for k, v in val.items()},
                "leaves_per_s": steps_per_epoch * gb / dt, "epoch_s": dt, "lr": last["lr"]}
+        if args.eval_precision == "bf16":
+            rec.update({f"val_bf16_{k}": v for k, v in vb.items()})
+            log(f"         | Val recon fp32: {val['recon_error']:.6f} | Val recon bf16 inference: {vb['recon_error']:.6f}")
         history.append(rec)
         log(f"Epoch {epoch + 1:02d}/{args.epochs} | Train Loss: {rec['train_loss']:.6f} | Val Loss: {val_loss:.6f} | "
             f"Perplexity: {last['perplexity']:.2f} | {rec['leaves_per_s'] / 1e3:.1f} k leaves/s ({dt:.2f} s/epoch)")
@@ -316,6 +344,8 @@ def main(argv=None):
     p.add_argument("--resume", type=str, default=None, help="checkpoint (.npz written as --model_path) to continue from")
     p.add_argument("--export-pack", dest="export_pack", action="store_true",
                    help="also write <model_path>_final.vqw: the input pack with the trained parameters and codebook")
+    p.add_argument("--eval-precision", dest="eval_precision", choices=("fp32", "bf16"), default="fp32",
+                   help="bf16: after each epoch also report the validation reconstruction sums of the bf16-operand inference mode (training stays fp32)")
     p.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl = RCCL)")
     p.add_argument("--single_gpu_rehearsal", action="store_true", help="tests: every rank on cuda:0 (use with --backend gloo)")
     p.set_defaults(func=train)
