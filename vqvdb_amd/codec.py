@@ -118,6 +118,9 @@ VEC3_FULLTRAIN_SYMBOLS = [
 # every symbol include/vqvdb_hip_vec3_precision.h declares (Vec3 inference precision mode; kept apart from the lists above)
 VEC3_PRECISION_SYMBOLS = ["vqhip_vec3_set_precision", "vqhip_vec3_get_precision"]
 VEC3_PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_VEC3_PRECISION_*
+# every symbol include/vqvdb_hip_vec3_bounded.h declares (Vec3 error-bounded round trip; kept apart from the lists above)
+VEC3_BOUNDED_SYMBOLS = ["vqhip_vec3_roundtrip_device", "vqhip_vec3_select_outliers_device", "vqhip_vec3_compress_bounded"]
+VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
 
@@ -258,6 +261,12 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_set_precision.argtypes = [vp, ci]
     lib.vqhip_vec3_get_precision.argtypes = [vp, vp]
     for name in VEC3_PRECISION_SYMBOLS:
+        getattr(lib, name).restype = ci
+    # include/vqvdb_hip_vec3_bounded.h
+    lib.vqhip_vec3_roundtrip_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.vqhip_vec3_select_outliers_device.argtypes = [vp, vp, i64, cf, vp, vp, vp]
+    lib.vqhip_vec3_compress_bounded.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp]
+    for name in VEC3_BOUNDED_SYMBOLS:
         getattr(lib, name).restype = ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
@@ -464,6 +473,84 @@ class HipVec3Codec:
     def train_set_state(self, embedding=None, cluster_size=None, embed_avg=None):
         arrs = self.check_state(self.model_info()["num_codes"], embedding, cluster_size, embed_avg)
         self._check(self._lib.vqhip_vec3_train_set_state(self._h, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    # ---- error-bounded round trip: include/vqvdb_hip_vec3_bounded.h ----
+    @staticmethod
+    def check_tol(tol) -> float:
+        """A real number, NaN included (NaN selects every leaf) -> the float32 value the kernel compares with; the selection
+        is ``~(leaf_err[:, 0] <= tol)``."""
+        if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)):
+            raise TypeError(f"tol must be a real number, got {tol!r}")
+        with np.errstate(over="ignore"):
+            t = np.float32(tol)
+        if float(t) > float(tol):   # the kernel compares in float32: round down, so that err <= t implies err <= tol
+            t = np.nextafter(t, np.float32(-np.inf))
+        return float(t)
+
+    def roundtrip_device(self, leaves_ptr: int, n: int, leaf_err_ptr: int, idx_ptr: int = 0, recon_ptr: int = 0, stream: int = 0):
+        if not leaf_err_ptr:
+            raise ValueError("leaf_err_ptr is NULL: the leaf errors need a device buffer of n * 2 float32")
+        self._check(self._lib.vqhip_vec3_roundtrip_device(self._h, leaves_ptr, n, idx_ptr or None, recon_ptr or None, leaf_err_ptr, stream or None))
+
+    def select_outliers_device(self, leaf_err_ptr: int, n: int, tol: float, ids_ptr: int, count_ptr: int, stream: int = 0):
+        if not count_ptr:
+            raise ValueError("count_ptr is NULL: the count needs a device buffer of one int64")
+        self._check(self._lib.vqhip_vec3_select_outliers_device(self._h, leaf_err_ptr, n, self.check_tol(tol), ids_ptr, count_ptr, stream or None))
+
+    def _compress_bounded_host(self, leaves: np.ndarray, tol: float):
+        n = leaves.shape[0]
+        idx, err = np.empty((n, 64), dtype=np.uint16), np.empty((n, VEC3_ERR_FLOATS), dtype=np.float32)
+        ids, count = np.empty(n, dtype=np.int64), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_compress_bounded(self._h, leaves.ctypes.data, n, tol, idx.ctypes.data, err.ctypes.data, ids.ctypes.data,
+                                                          ctypes.byref(count)))
+        return idx, err, ids[:count.value].copy()
+
+    def roundtrip(self, leaves, return_recon: bool = False):
+        """Encode and decode in one pass -> (indices [n,64], leaf_err [n,2] = per leaf max |x - x^| and sum (x - x^)^2
+        [, recon [n,512,3]]).  A float32 torch tensor on the handle's device gives device tensors (indices int16, the bits of
+        the uint16 codes), ordered on torch's current stream (complete on return where that is the default stream); a numpy
+        array goes through the host entry points."""
+        if isinstance(leaves, np.ndarray):
+            leaves = self.check_leaves(leaves)
+            idx, err, _ = self._compress_bounded_host(leaves, float("inf"))
+            return (idx, err, self.decode(idx)) if return_recon else (idx, err)
+        import torch
+        if not (isinstance(leaves, torch.Tensor) and leaves.is_cuda and leaves.dtype == torch.float32 and leaves.is_contiguous()):
+            raise TypeError("vec3 leaves must be a float32 numpy array or a contiguous float32 torch tensor on the GPU")
+        if tuple(leaves.shape[1:]) not in ((512, 3), (8, 8, 8, 3)):
+            raise ValueError(f"vec3 leaves must have shape [n,512,3] or [n,8,8,8,3], got {list(leaves.shape)}")
+        n = leaves.shape[0]
+        idx = torch.empty((n, 64), dtype=torch.int16, device=leaves.device)
+        err = torch.empty((n, VEC3_ERR_FLOATS), dtype=torch.float32, device=leaves.device)
+        rec = torch.empty((n, 512, 3), dtype=torch.float32, device=leaves.device) if return_recon else None
+        st = torch.cuda.current_stream(leaves.device).cuda_stream
+        if st == 0:   # a null handle means the codec's own stream: order it after the producer of `leaves` by hand
+            torch.cuda.synchronize(leaves.device)
+        self.roundtrip_device(leaves.data_ptr(), n, err.data_ptr(), idx.data_ptr(), rec.data_ptr() if return_recon else 0, st)
+        if st == 0:
+            torch.cuda.synchronize(leaves.device)
+        return (idx, err, rec) if return_recon else (idx, err)
+
+    def compress_bounded(self, leaves: np.ndarray, tol: float, return_leaf_err: bool = False):
+        """-> (indices [n,64], outlier_ids int64 ascending, outlier_leaves [m,512,3]): the leaves whose largest error is over
+        ``tol`` (or not finite) come back as raw copies, so that decompress_bounded stays within tol on every value."""
+        leaves = self.check_leaves(leaves)
+        idx, err, ids = self._compress_bounded_host(leaves, self.check_tol(tol))
+        out = (idx, ids, leaves[ids].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def decompress_bounded(self, indices: np.ndarray, outlier_ids, outlier_leaves) -> np.ndarray:
+        """Decoded leaves [n,512,3] with the leaves ``outlier_ids`` overwritten by their raw copies."""
+        indices = self.check_indices(indices)
+        ids = np.asarray(outlier_ids, dtype=np.int64).reshape(-1)
+        raw = np.asarray(outlier_leaves, dtype=np.float32).reshape(-1, 512, 3)
+        if len(ids) != len(raw):
+            raise ValueError(f"{len(ids)} outlier ids but {len(raw)} outlier leaves")
+        if len(ids) and (ids.min() < 0 or ids.max() >= indices.shape[0]):
+            raise ValueError(f"outlier ids must be in [0, {indices.shape[0]})")
+        out = self.decode(indices)
+        out[ids] = raw
+        return out
 
     # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----
     @staticmethod

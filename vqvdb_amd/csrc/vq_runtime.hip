@@ -2739,5 +2739,6 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_train_full.inc"
 #include "vq_vec3.inc"
 #include "vq_vec3_bf16.inc"
+#include "vq_vec3_bounded.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"

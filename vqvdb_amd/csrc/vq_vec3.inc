@@ -32,6 +32,12 @@ struct vqhip_vec3_codec {
     float *ft_P = nullptr, *ft_M = nullptr, *ft_V = nullptr;
     float* ft_ws = nullptr;            // activations, gradients and partials of ft_leaves leaves (v3f_ws_bytes)
     int64_t ft_leaves = 0;
+    // error-bounded round trip (vq_vec3_bounded.inc)
+    int64_t* bd_scan = nullptr;        // selection: per-block counts / offsets [bd_scan_n]
+    int64_t bd_scan_n = 0;
+    float* bd_err = nullptr;           // host entry point: leaf errors [bd_n][2]
+    int64_t* bd_ids = nullptr;         // host entry point: outlier ids [bd_n], then their count
+    int64_t bd_n = 0;
     struct Dbg {
         float* p = nullptr;
         int64_t cap = 0, n = 0;
@@ -416,8 +422,9 @@ int v3_encode_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_
     return v3_launch_check(c, "vec3 quantizer");
 }
 
-// the decoder from decoder.stem on, reading its input [m][64][64] from W.z (workspace of at least m leaves)
-int v3_decode_from_z(vqhip_vec3_codec* c, int64_t m, float* out, hipStream_t s)
+// the decoder from decoder.stem to decoder.up_conv, reading its input [m][64][64] from W.z (workspace of at least m leaves);
+// leaves W.u for the tail (final_k, or final_err_k of vq_vec3_bounded.inc)
+int v3_decode_body(vqhip_vec3_codec* c, int64_t m, hipStream_t s)
 {
     const V3Ws W = v3_ws(c);
     auto& w = c->w;
@@ -435,8 +442,15 @@ int v3_decode_from_z(vqhip_vec3_codec* c, int64_t m, float* out, hipStream_t s)
     v3::ConvArgs a = v3_args(W.p, w["d.up.wf"], w["d.up.b"], W.u);
     a.gate = W.gate;
     v3_conv(v3_up, L_up{}, s, m, a, 2);
-    if ((rc = v3_launch_check(c, "vec3 decoder.up_conv")) || (rc = v3_keep(c, "decoder.up_conv", W.u, 256 * 64, m, s))) return rc;
-    hipLaunchKernelGGL(v3::final_k, dim3(nb), dim3(512), V3_LDS_FINAL, s, W.u, w["d.final.w"], w["d.final.b"], out, m);
+    if ((rc = v3_launch_check(c, "vec3 decoder.up_conv"))) return rc;
+    return v3_keep(c, "decoder.up_conv", W.u, 256 * 64, m, s);
+}
+
+// the decoder from decoder.stem on
+int v3_decode_from_z(vqhip_vec3_codec* c, int64_t m, float* out, hipStream_t s)
+{
+    if (int rc = v3_decode_body(c, m, s)) return rc;
+    hipLaunchKernelGGL(v3::final_k, dim3((unsigned)m), dim3(512), V3_LDS_FINAL, s, v3_ws(c).u, c->w["d.final.w"], c->w["d.final.b"], out, m);
     return v3_launch_check(c, "vec3 decoder.final");
 }
 
@@ -450,6 +464,7 @@ int v3_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* 
 // vq_vec3_bf16.inc: the same chunks with bf16 convolution operands
 int v3b_encode_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_t* idx, hipStream_t s);
 int v3b_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s);
+int v3b_decode_body(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, hipStream_t s);   // gather to decoder.up_conv
 
 // the public entry points follow the handle's precision mode (training calls v3_encode_chunk / v3_decode_from_z: always fp32)
 int v3_encode_mode(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_t* idx, hipStream_t s)
@@ -555,6 +570,9 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     if (c->tr_avg) hipFree(c->tr_avg);
     if (c->tr_ws) hipFree(c->tr_ws);
     if (c->ft_ws) hipFree(c->ft_ws);
+    if (c->bd_scan) hipFree(c->bd_scan);
+    if (c->bd_err) hipFree(c->bd_err);
+    if (c->bd_ids) hipFree(c->bd_ids);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }

@@ -150,9 +150,9 @@ int v3b_encode_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16
     return v3_launch_check(c, "vec3 quantizer");
 }
 
-int v3b_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s)
+// gather to decoder.up_conv with the bf16 convolutions; leaves W.u for the tail
+int v3b_decode_body(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, hipStream_t s)
 {
-    if (int rc = v3_ensure_ws(c, m)) return rc;
     const V3Ws W = v3_ws(c);
     auto& w = c->w;
     const unsigned nb = (unsigned)m;
@@ -170,8 +170,15 @@ int v3b_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float*
     v3::ConvArgs a = v3_args(W.p, w["d.up.wb"], w["d.up.b"], W.u);
     a.gate = W.gate;
     v3b_conv(v3b_up, LB_up{}, s, m, a);
-    if ((rc = v3_launch_check(c, "vec3 bf16 decoder.up_conv")) || (rc = v3_keep(c, "decoder.up_conv", W.u, 256 * 64, m, s))) return rc;
-    hipLaunchKernelGGL(v3::final_k, dim3(nb), dim3(512), V3_LDS_FINAL, s, W.u, w["d.final.w"], w["d.final.b"], out, m);
+    if ((rc = v3_launch_check(c, "vec3 bf16 decoder.up_conv"))) return rc;
+    return v3_keep(c, "decoder.up_conv", W.u, 256 * 64, m, s);
+}
+
+int v3b_decode_chunk(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* out, hipStream_t s)
+{
+    if (int rc = v3_ensure_ws(c, m)) return rc;
+    if (int rc = v3b_decode_body(c, idx, m, s)) return rc;
+    hipLaunchKernelGGL(v3::final_k, dim3((unsigned)m), dim3(512), V3_LDS_FINAL, s, v3_ws(c).u, c->w["d.final.w"], c->w["d.final.b"], out, m);
     return v3_launch_check(c, "vec3 decoder.final");
 }
 

@@ -34,7 +34,7 @@ import torch.distributed as dist
 from vqvdb_amd.codebook_training import allreduce_stats
 from vqvdb_amd.codec import HipVec3Codec
 from vqvdb_amd.full_training import cosine_lr
-from vqvdb_amd.vec3_training import (DEAD_CODE_RESET_INTERVAL, Vec3CodebookTrainer, _leaves_arg, load_leaves, metrics_from_stats,
+from vqvdb_amd.vec3_training import (DEAD_CODE_RESET_INTERVAL, Vec3CodebookTrainer, _leaves_arg, leaf_error_line, load_leaves, metrics_from_stats,
                                      split_train_val, stats_floats)
 
 D = 64
@@ -285,11 +285,15 @@ def train(args) -> dict:
                 log(f"INFO: Resetting {n_dead} dead codes.")
         val = {"recon_error": 0.0, "vq_loss": 0.0, "recon_mse": 0.0, "recon_l1": 0.0}
         n_val = max(len(va_ids) // gb, 1)
+        vbatches = []
         for step in range(n_val):
             ids = shard(va_ids, step) if len(va_ids) >= gb else va_ids[rank::world]
-            mv = trainer.evaluate(d_all[torch.from_numpy(ids).to(device)])
+            vbatch = d_all[torch.from_numpy(ids).to(device)]
+            mv = trainer.evaluate(vbatch)
             for k in val:
                 val[k] += mv[k] / n_val
+            if args.report_leaf_error:
+                vbatches.append(vbatch)
         val_loss = val["recon_error"] + val["vq_loss"]
         if args.eval_precision == "bf16":   # the same validation batches through encode / decode in bf16-operand mode
             vb = {"recon_mse": 0.0, "recon_l1": 0.0}
@@ -309,6 +313,8 @@ def train(args) -> dict:
         history.append(rec)
         log(f"Epoch {epoch + 1:02d}/{args.epochs} | Train Loss: {rec['train_loss']:.6f} | Val Loss: {val_loss:.6f} | "
             f"Perplexity: {last['perplexity']:.2f} | {rec['leaves_per_s'] / 1e3:.1f} k leaves/s ({dt:.2f} s/epoch)")
+        if args.report_leaf_error:
+            log(leaf_error_line(codec, vbatches))
         if val_loss < best_val and rank == 0:
             best_val = val_loss
             np.savez(args.model_path, epoch=epoch + 1, best_val_loss=best_val, **trainer.checkpoint())
@@ -346,6 +352,8 @@ def main(argv=None):
                    help="also write <model_path>_final.vqw: the input pack with the trained parameters and codebook")
     p.add_argument("--eval-precision", dest="eval_precision", choices=("fp32", "bf16"), default="fp32",
                    help="bf16: after each epoch also report the validation reconstruction sums of the bf16-operand inference mode (training stays fp32)")
+    p.add_argument("--report-leaf-error", dest="report_leaf_error", action="store_true",
+                   help="after each validation also print the per-leaf largest reconstruction error (median, 99th percentile, worst leaf)")
     p.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl = RCCL)")
     p.add_argument("--single_gpu_rehearsal", action="store_true", help="tests: every rank on cuda:0 (use with --backend gloo)")
     p.set_defaults(func=train)

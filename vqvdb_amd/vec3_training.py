@@ -179,6 +179,14 @@ def export_pack(pack_path: str, state: dict, out_path: str):
     weightpack.save(out_path, t)
 
 
+def leaf_error_line(codec, batches) -> str:
+    """--report-leaf-error: the per-leaf largest error |x - x^| of the given validation batches through
+    HipVec3Codec.roundtrip (inference path, the handle's precision mode): median, 99th percentile and the worst leaf."""
+    worst = torch.cat([codec.roundtrip(b.contiguous())[1][:, 0] for b in batches]).double().cpu().numpy()
+    p50, p99, p100 = np.percentile(worst, [50, 99, 100])
+    return f"         | Leaf max error over {len(worst)} val leaves: p50 {p50:.6f} | p99 {p99:.6f} | p100 (worst leaf) {p100:.6f}"
+
+
 def train(args) -> dict:
     from vqvdb_amd.sharding import shard_range
     distributed = "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1
@@ -236,17 +244,23 @@ def train(args) -> dict:
                 log(f"INFO: Resetting {n_dead} dead codes.")
         val = {"recon_error": 0.0, "vq_loss": 0.0, "recon_mse": 0.0, "recon_l1": 0.0}
         n_val = max(len(va_ids) // gb, 1)
+        vbatches = []
         for step in range(n_val):
             ids = shard(va_ids, step) if len(va_ids) >= gb else va_ids[rank::world]
-            mv = trainer.evaluate(d_all[torch.from_numpy(ids).to(device)])
+            vbatch = d_all[torch.from_numpy(ids).to(device)]
+            mv = trainer.evaluate(vbatch)
             for k in val:
                 val[k] += mv[k] / n_val
+            if args.report_leaf_error:
+                vbatches.append(vbatch)
         val_loss = val["recon_error"] + val["vq_loss"]
         rec = {"epoch": epoch + 1, "train_vq_loss": last["vq_loss"], "perplexity": last["perplexity"], "codes_used": last["codes_used"],
                "val_loss": val_loss, **{f"val_{k}": v for k, v in val.items()}, "leaves_per_s": steps_per_epoch * gb / dt, "epoch_s": dt}
         history.append(rec)
         log(f"Epoch {epoch + 1:02d}/{args.epochs} | Train VQ: {last['vq_loss']:.6f} | Val Loss: {val_loss:.6f} | "
             f"Perplexity: {last['perplexity']:.2f} | {rec['leaves_per_s'] / 1e3:.1f} k leaves/s ({dt:.2f} s/epoch)")
+        if args.report_leaf_error:
+            log(leaf_error_line(codec, vbatches))
         if val_loss < best_val and rank == 0:
             best_val = val_loss
             np.savez(args.model_path, epoch=epoch + 1, best_val_loss=best_val, **trainer.state_dict())
@@ -281,6 +295,8 @@ def main(argv=None):
     p.add_argument("--resume", type=str, default=None, help="checkpoint (.npz written as --model_path) to continue from")
     p.add_argument("--export-pack", dest="export_pack", action="store_true",
                    help="also write <model_path>_final.vqw: the input pack with the trained quantizer.embedding")
+    p.add_argument("--report-leaf-error", dest="report_leaf_error", action="store_true",
+                   help="after each validation also print the per-leaf largest reconstruction error (median, 99th percentile, worst leaf)")
     p.add_argument("--backend", type=str, default="nccl", help="torch.distributed backend (nccl = RCCL)")
     p.add_argument("--single_gpu_rehearsal", action="store_true", help="tests: every rank on cuda:0 (use with --backend gloo)")
     p.set_defaults(func=train)
