@@ -17,7 +17,8 @@ import torch
 import torch.distributed as dist
 
 from vqvdb_amd import synth
-from vqvdb_amd.codebook_training import STATS_FLOATS, allreduce_stats, dead_code_reset, metrics_from_stats
+from vqvdb_amd.codebook_training import D, K, STATS_FLOATS, metrics_from_stats
+from vqvdb_amd.training_common import TrainerBase, recon_metrics
 
 AUX_FLOATS = STATS_FLOATS + 3
 TRAINABLE = [(name, shape) for name, shape, _ in synth.TENSORS if not name.startswith("quantizer.")]
@@ -44,42 +45,35 @@ def cosine_lr(base_lr: float, step: int, t_max: int, eta_min: float = 0.0) -> fl
     return eta_min + (base_lr - eta_min) * (1.0 + math.cos(math.pi * step / t_max)) / 2.0
 
 
-class FullTrainer:
+class FullTrainer(TrainerBase):
     """Drives vqhip_fulltrain_* for one rank.  `codec` is a vqvdb_amd.codec.HipCodec on this rank's device."""
+    leaf_values, k, d = 512, K, D
 
     def __init__(self, codec, lr: float = 1e-4, betas=(0.9, 0.999), adam_eps: float = 1e-8, weight_decay: float = 1e-4,
                  commitment_cost: float = 0.25, ema_decay: float = 0.95, ema_eps: float = 1e-4, t_max: Optional[int] = None, group=None,
                  device: str = "cuda", overlap: bool = True):
-        self.codec, self.group, self.device = codec, group, torch.device(device)
-        self.lr, self.betas, self.adam_eps, self.weight_decay = lr, betas, adam_eps, weight_decay
-        self.commitment_cost, self.ema_decay, self.ema_eps, self.t_max = commitment_cost, ema_decay, ema_eps, t_max
         if abs(commitment_cost - 0.25) > 1e-12:
             raise ValueError("the kernels fix commitment_cost = 0.25 (training.py:55)")
+        super().__init__(codec, commitment_cost, ema_decay, ema_eps, group, device)
+        self.lr, self.betas, self.adam_eps, self.weight_decay, self.t_max = lr, betas, adam_eps, weight_decay, t_max
         codec.fulltrain_begin()
         self.grads = torch.zeros(codec.fulltrain_param_count(), dtype=torch.float32, device=self.device)
         self.aux = torch.zeros(AUX_FLOATS, dtype=torch.float32, device=self.device)
-        self.stream = torch.cuda.Stream(device=self.device)
         self.comm_stream = torch.cuda.Stream(device=self.device)   # all-reduce of the decoder's gradients, overlapped with the encoder backward
         self.overlap = overlap
         self.steps_done = 0
+        self.kept_batch = None   # the last batch stepped with keep_latent (dead-code reset input)
 
-    def _world(self) -> int:
-        return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
-
-    def step(self, leaves: torch.Tensor, want_metrics: bool = True) -> Optional[dict]:
+    def step(self, leaves: torch.Tensor, want_metrics: bool = True, keep_latent: bool = False) -> Optional[dict]:
         """One optimizer step on this rank's batch (float32, 512 values per leaf, resident on the device; every rank passes the
-        same number of leaves)."""
-        leaves = leaves.contiguous()
-        if leaves.dtype != torch.float32 or leaves.numel() % 512:
-            raise ValueError("leaves must be float32 with 512 values per leaf")
-        n = leaves.numel() // 512
+        same number of leaves).  keep_latent remembers the batch: reset_dead_codes() computes its encoder outputs when it runs."""
+        leaves, n = self._leaves_arg(leaves)
+        if keep_latent:
+            self.kept_batch = leaves
         world = self._world()
         lr = self.lr if self.t_max is None else cosine_lr(self.lr, self.steps_done, self.t_max)
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
         out = None
-        with torch.cuda.stream(self.stream):
-            h = self.stream.cuda_stream
+        with self._side_stream(leaves) as h:
             if world > 1 and self.overlap:
                 # the decoder's gradients (69 % of the vector) are final once the decoder half of the backward pass is enqueued: their
                 # all-reduce runs on its own stream while the encoder half computes; encoder slice + statistics follow on this stream
@@ -105,62 +99,34 @@ class FullTrainer:
                     dist.all_reduce(self.grads, op=dist.ReduceOp.SUM, group=self.group)
                     dist.all_reduce(self.aux, op=dist.ReduceOp.SUM, group=self.group)
             self.codec.fulltrain_apply_device(self.grads.data_ptr(), self.aux.data_ptr(), lr, self.steps_done + 1, self.betas, self.adam_eps,
-                                              self.weight_decay, self.ema_decay, self.ema_eps, stream=h)
+                                              self.weight_decay, self.decay, self.eps, stream=h)
             if want_metrics:
                 aux = self.aux.cpu().numpy().astype(np.float64)
                 out = metrics_from_stats(aux[:STATS_FLOATS], self.commitment_cost)
-                sq, ab, vox = aux[STATS_FLOATS:]
-                out.update(recon_mse=float(sq / vox), recon_l1=float(ab / vox), lr=lr)
-                out["recon_error"] = 0.8 * out["recon_mse"] + 0.2 * out["recon_l1"]
-                out["loss"] = out["recon_error"] + out["vq_loss"]
-        leaves.record_stream(self.stream)
-        cur.wait_stream(self.stream)
+                mse, l1, mix = recon_metrics(aux[STATS_FLOATS:])
+                out.update(recon_mse=mse, recon_l1=l1, lr=lr, recon_error=mix, loss=mix + out["vq_loss"])
         self.steps_done += 1
         return out
 
-    def evaluate(self, leaves: torch.Tensor, mse_weight: float = 0.8, l1_weight: float = 0.2) -> dict:
-        """Validation forward (training.py:183-199) with the current weights through the inference kernels: reconstruction MSE / L1,
-        vq_loss and perplexity over the GLOBAL batch; nothing is updated."""
-        leaves = leaves.contiguous()
-        n = leaves.numel() // 512
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            buf = torch.zeros(STATS_FLOATS + 3, dtype=torch.float32, device=self.device)
-            self.codec.train_eval_device(leaves.data_ptr(), n, buf.data_ptr(), buf[STATS_FLOATS:].data_ptr(), stream=self.stream.cuda_stream)
-            allreduce_stats(buf, self.group)
-            host = buf.cpu().numpy().astype(np.float64)
-        leaves.record_stream(self.stream)
-        cur.wait_stream(self.stream)
-        out = metrics_from_stats(host[:STATS_FLOATS], self.commitment_cost)
-        sq, ab, elems = host[STATS_FLOATS:]
-        out.update(recon_mse=float(sq / elems), recon_l1=float(ab / elems))
-        out["recon_error"] = mse_weight * out["recon_mse"] + l1_weight * out["recon_l1"]
-        return out
-
-    def reset_dead_codes(self, leaves: torch.Tensor, threshold: float = 1.0, generator=None) -> int:
-        """check_and_reset_dead_codes (VQVAE_v2.py:382-417) from the encoder outputs of `leaves` under the current weights."""
-        leaves = leaves.contiguous()
-        n = leaves.numel() // 512
-        z = torch.empty((n * 64, 128), dtype=torch.float32, device=self.device)
+    def reset_dead_codes(self, leaves: Optional[torch.Tensor] = None, threshold: float = 1.0, generator=None) -> int:
+        """check_and_reset_dead_codes (VQVAE_v2.py:382-417) from the encoder outputs of `leaves` (default: the batch kept by
+        step(..., keep_latent=True)) under the current weights."""
+        leaves = self.kept_batch if leaves is None else leaves
+        if leaves is None:
+            raise ValueError("no batch kept: call step(..., keep_latent=True) first or pass leaves")
+        leaves, n = self._leaves_arg(leaves)
+        z = torch.empty((n * 64, D), dtype=torch.float32, device=self.device)
         scratch = torch.zeros(STATS_FLOATS, dtype=torch.float32, device=self.device)
-        with torch.cuda.stream(self.stream):
-            self.stream.wait_stream(torch.cuda.current_stream(self.device))
-            self.codec.train_vq_stats_device(leaves.data_ptr(), n, scratch.data_ptr(), latent_ptr=z.data_ptr(), stream=self.stream.cuda_stream)
-        self.stream.synchronize()
-        st = {k: torch.from_numpy(v).to(self.device) for k, v in self.codec.train_get_state().items()}
-        k = dead_code_reset(st, z, threshold, generator, self.group)
-        if k:
-            self.codec.train_set_state(**{kk: v.cpu().numpy() for kk, v in st.items()})
-        return k
+        with self._side_stream(leaves) as h:
+            self.codec.train_vq_stats_device(leaves.data_ptr(), n, scratch.data_ptr(), latent_ptr=z.data_ptr(), stream=h)
+        return super().reset_dead_codes(z, threshold, generator)
 
     def state_dict(self) -> dict:
         """Model state in the reference's state_dict naming (parameters + quantizer buffers)."""
-        sd = flat_to_dict(self.codec.fulltrain_get_params())
-        sd.update({f"quantizer.{k}": v for k, v in self.codec.train_get_state().items()})
-        return sd
+        return {**flat_to_dict(self.codec.fulltrain_get_params()), **super().state_dict()}
 
     def load_state_dict(self, sd: dict):
+        """A state dict of weights alone (no cluster_size / embed_avg) loads too: those buffers then stay as they are."""
         self.codec.fulltrain_set_params(dict_to_flat(sd))
         self.codec.train_set_state(embedding=sd["quantizer.embedding"], cluster_size=sd.get("quantizer.cluster_size"),
                                    embed_avg=sd.get("quantizer.embed_avg"))

@@ -22,23 +22,20 @@ latent, validation, a best-validation checkpoint and a final save.
 from __future__ import annotations
 
 import argparse
-import os
 import sys
-import time
 from typing import Optional
 
 import numpy as np
 import torch
 import torch.distributed as dist
 
-from vqvdb_amd.codebook_training import allreduce_stats
 from vqvdb_amd.codec import HipVec3Codec
 from vqvdb_amd.full_training import cosine_lr
-from vqvdb_amd.vec3_training import (DEAD_CODE_RESET_INTERVAL, Vec3CodebookTrainer, _leaves_arg, leaf_error_line, load_leaves, metrics_from_stats,
-                                     split_train_val, stats_floats)
+from vqvdb_amd.training_common import LoopSpec, TrainerBase, allreduce_stats, recon_metrics, run_training, split_train_val
+from vqvdb_amd.vec3_training import TRAIN_FRACTION, leaf_error_line, load_leaves, metrics_from_stats, stats_floats
 
 D = 64
-MSE_WEIGHT, L1_WEIGHT = 0.8, 0.2
+SPEC = LoopSpec(train_loss="mean", pass_n_global=True, record_lr=True, final_checkpoint=True)
 
 
 def losses_from_aux(aux: np.ndarray, k: int, commitment_cost: float = 0.25) -> dict:
@@ -46,38 +43,29 @@ def losses_from_aux(aux: np.ndarray, k: int, commitment_cost: float = 0.25) -> d
     aux = np.asarray(aux, np.float64)
     nf = stats_floats(k)
     out = metrics_from_stats(aux[:nf], k, commitment_cost)
-    sq, ab, elems = aux[nf:nf + 3]
-    out["mse"] = float(sq / max(elems, 1.0))
-    out["l1"] = float(ab / max(elems, 1.0))
-    out["recon"] = MSE_WEIGHT * out["mse"] + L1_WEIGHT * out["l1"]
+    out["mse"], out["l1"], out["recon"] = recon_metrics(aux[nf:nf + 3])
     out["loss"] = out["recon"] + out["vq_loss"]
     return out
 
 
-class Vec3FullTrainer:
-    """Drives vqhip_vec3_fulltrain_* for one rank.  `codec` is a vqvdb_amd.codec.HipVec3Codec on this rank's device."""
+class Vec3FullTrainer(TrainerBase):
+    """Drives vqhip_vec3_fulltrain_* for one rank.  `codec` is a vqvdb_amd.codec.HipVec3Codec on this rank's device.
+    evaluate() is the stage-1 eval forward: it runs the handle's live tables, which apply rebuilds from the trained parameters."""
+    leaf_values, d = 1536, D
 
     def __init__(self, codec, lr: float = 5e-4, betas=(0.9, 0.999), adam_eps: float = 1e-8, weight_decay: float = 1e-4,
                  decay: float = 0.95, eps: float = 1e-4, group=None, device: str = "cuda", commitment_cost: float = 0.25):
-        HipVec3Codec.check_ema(decay, eps)
         HipVec3Codec.check_adamw(lr, 1, betas, adam_eps, weight_decay)
-        self.codec, self.group = codec, group
+        super().__init__(codec, commitment_cost, decay, eps, group, device)
         self.lr, self.betas, self.adam_eps, self.weight_decay = lr, tuple(betas), adam_eps, weight_decay
-        self.decay, self.eps, self.commitment_cost = decay, eps, commitment_cost
-        self.device = torch.device(device)
         self.k = codec.model_info()["num_codes"]
         codec.fulltrain_begin()
         self.np = codec.fulltrain_param_count()
         self.naux = codec.fulltrain_aux_floats()
         self.grads = torch.zeros(self.np, dtype=torch.float32, device=self.device)
         self.aux = torch.zeros(self.naux, dtype=torch.float32, device=self.device)
-        self.stream = torch.cuda.Stream(device=self.device)
         self.step_count = 0
         self.sched_t, self.t_max = 0, None   # scheduler position (host cosine annealing when t_max is set)
-        self.latent = None
-
-    def _world(self) -> int:
-        return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
 
     def current_lr(self) -> float:
         return self.lr if self.t_max is None else cosine_lr(self.lr, self.sched_t, self.t_max)
@@ -86,23 +74,16 @@ class Vec3FullTrainer:
              lr: Optional[float] = None) -> Optional[dict]:
         """One optimizer step on this rank's batch (float32 [n,512,3] or [n,8,8,8,3] on the device).  n_global defaults to
         the all-reduced sum of the ranks' n.  -> loss, recon, vq_loss, perplexity (global batch, before the update)."""
-        leaves, n = _leaves_arg(leaves)
+        leaves, n = self._leaves_arg(leaves)
         if n_global is None:
             t = torch.tensor([n], dtype=torch.int64)
             if self._world() > 1:
                 dist.all_reduce(t, group=self.group)
             n_global = int(t.item())
         lr = self.current_lr() if lr is None else lr
-        cur = torch.cuda.current_stream(self.device)
-        self.stream.wait_stream(cur)
         out = None
-        with torch.cuda.stream(self.stream):
-            zptr = 0
-            if keep_latent:
-                if self.latent is None or self.latent.shape[0] != n * 64:
-                    self.latent = torch.empty((n * 64, D), dtype=torch.float32, device=self.device)
-                zptr = self.latent.data_ptr()
-            h = self.stream.cuda_stream
+        with self._side_stream(leaves) as h:
+            zptr = self._latent_ptr(n, keep_latent)
             self.codec.fulltrain_fwdbwd_device(leaves.data_ptr(), n, n_global, self.grads.data_ptr(), self.aux.data_ptr(), zptr, stream=h)
             allreduce_stats(self.grads, self.group)
             allreduce_stats(self.aux, self.group)
@@ -112,53 +93,31 @@ class Vec3FullTrainer:
             if want_metrics:
                 out = losses_from_aux(self.aux.cpu().numpy(), self.k, self.commitment_cost)
                 out["lr"] = lr
-        leaves.record_stream(self.stream)
-        cur.wait_stream(self.stream)
         if self.t_max is not None:
             self.sched_t += 1
         return out
 
-    def evaluate(self, leaves: torch.Tensor) -> dict:
-        """Validation forward in eval mode (training.py:183-199) on the live model: recon (0.8 mse + 0.2 l1), mse, l1, vq_loss,
-        perplexity over the global batch; nothing is updated."""
-        # the stage-1 eval forward runs the handle's live tables, which apply rebuilds from the trained parameters
-        return Vec3CodebookTrainer.evaluate(self, leaves)
-
-    def reset_dead_codes(self, flat_z: Optional[torch.Tensor] = None, threshold: float = 1.0, generator=None) -> int:
-        """check_and_reset_dead_codes (VQVAE_v2.py:382-417) on the kept latent (or `flat_z` [rows, 64])."""
-        return Vec3CodebookTrainer.reset_dead_codes(self, flat_z, threshold, generator)
-
     def state_dict(self) -> dict:
         """The model in the reference's state_dict naming: every parameter and the quantizer buffers."""
-        sd = vec_to_state(self.codec.fulltrain_get_params())
-        sd.update({f"quantizer.{k}": v for k, v in self.codec.train_get_state().items()})
-        return sd
+        return {**vec_to_state(self.codec.fulltrain_get_params()), **super().state_dict()}
 
     def load_state_dict(self, sd: dict):
         self.codec.fulltrain_set_params(state_to_vec(sd))
-        self.codec.train_set_state(embedding=sd["quantizer.embedding"], cluster_size=sd["quantizer.cluster_size"],
-                                   embed_avg=sd["quantizer.embed_avg"])
+        super().load_state_dict(sd)
 
     def checkpoint(self) -> dict:
         """Everything a bit-exact resume needs: parameters, both Adam moments, step, EMA buffers, scheduler position."""
         m, v = self.codec.fulltrain_get_opt_state()
-        ck = {"params": self.codec.fulltrain_get_params(), "exp_avg": m, "exp_avg_sq": v, "step": np.int64(self.step_count),
-              "sched_t": np.int64(self.sched_t), "t_max": np.int64(-1 if self.t_max is None else self.t_max)}
-        ck.update({f"quantizer.{k}": val for k, val in self.codec.train_get_state().items()})
-        return ck
+        return {"params": self.codec.fulltrain_get_params(), "exp_avg": m, "exp_avg_sq": v, "step": np.int64(self.step_count),
+                "sched_t": np.int64(self.sched_t), "t_max": np.int64(-1 if self.t_max is None else self.t_max), **super().state_dict()}
 
     def load_checkpoint(self, ck: dict):
         self.codec.fulltrain_set_params(ck["params"])
         self.codec.fulltrain_set_opt_state(ck["exp_avg"], ck["exp_avg_sq"])
-        self.codec.train_set_state(embedding=ck["quantizer.embedding"], cluster_size=ck["quantizer.cluster_size"],
-                                   embed_avg=ck["quantizer.embed_avg"])
+        super().load_state_dict(ck)
         self.step_count = int(ck["step"])
         self.sched_t = int(ck["sched_t"])
         self.t_max = None if int(ck["t_max"]) < 0 else int(ck["t_max"])
-
-    def finish(self):
-        """Wait for the device; the handle then encodes / decodes with the trained model."""
-        torch.cuda.synchronize(self.device)
 
 
 # ---- flat vector <-> state_dict ----------------------------------------------------------------------------------------
@@ -227,108 +186,35 @@ def eval_roundtrip(codec, leaves: torch.Tensor) -> dict:
 
 # ---- epoch driver ------------------------------------------------------------------------------------------------------
 def train(args) -> dict:
-    from vqvdb_amd.sharding import shard_range
-    distributed = "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if distributed and not dist.is_initialized():
-        dist.init_process_group(args.backend, **({"device_id": torch.device("cuda", local)} if args.backend == "nccl" else {}))
-    if args.single_gpu_rehearsal:
-        local = 0
-    device = torch.device("cuda", local)
-    torch.cuda.set_device(device)
-    log = (lambda *a: print(*a, flush=True)) if rank == 0 else (lambda *a: None)
+    def build(local, device, world):
+        codec = HipVec3Codec(args.pack, device_id=local)
+        trainer = Vec3FullTrainer(codec, lr=args.lr, weight_decay=args.weight_decay, decay=args.decay, eps=args.eps, device=str(device))
+        leaves = load_leaves(args.data_dir, args.synthetic_leaves, args.seed)
+        tr_ids, va_ids = split_train_val(len(leaves), args.seed, TRAIN_FRACTION)
+        trainer.t_max = args.epochs * (len(tr_ids) // (args.batch_size * world))   # cosine annealing over all steps
+        return codec, trainer, leaves, tr_ids, va_ids
 
-    codec = HipVec3Codec(args.pack, device_id=local)
-    trainer = Vec3FullTrainer(codec, lr=args.lr, weight_decay=args.weight_decay, decay=args.decay, eps=args.eps, device=str(device))
-    leaves = load_leaves(args.data_dir, args.synthetic_leaves, args.seed)
-    tr_ids, va_ids = split_train_val(len(leaves), args.seed)
-    gb = args.batch_size * world
-    steps_per_epoch = len(tr_ids) // gb
-    if steps_per_epoch < 1:
-        raise SystemExit(f"training set of {len(tr_ids)} leaves is smaller than one global batch ({world} x {args.batch_size}); lower --batch_size")
-    if len(va_ids) < world:
-        raise SystemExit(f"validation set of {len(va_ids)} leaves cannot give each of the {world} ranks a leaf")
-    trainer.t_max = args.epochs * steps_per_epoch
-    log(f"Dataset: {len(leaves)} leaves, train {len(tr_ids)}, val {len(va_ids)}; {world} rank(s) x batch {args.batch_size}")
+    def export(trainer, path):
+        export_pack(args.pack, trainer.state_dict(), path)
+        return f"Vec3 weight pack with the trained model: {path}"
 
-    def shard(ids, step):
-        lo, hi = shard_range(gb, rank, world)
-        return ids[step * gb + lo: step * gb + hi]
-
-    d_all = torch.from_numpy(np.ascontiguousarray(leaves)).to(device)
-    best_val, history, start_epoch = float("inf"), [], 0
-    if args.resume:
-        ck = dict(np.load(args.resume))
-        start_epoch = int(ck.pop("epoch", 0))
-        best_val = float(ck.pop("best_val_loss", best_val))
-        trainer.load_checkpoint(ck)
-        log(f"Resumed from {args.resume} at epoch {start_epoch}")
-    os.makedirs(os.path.dirname(os.path.abspath(args.model_path)) or ".", exist_ok=True)
-    for epoch in range(start_epoch, args.epochs):
-        order = np.random.default_rng(args.seed + 1 + epoch).permutation(tr_ids)   # shuffle=True
-        t0 = time.perf_counter()
-        total, last = 0.0, None
-        for step in range(steps_per_epoch):
-            batch = d_all[torch.from_numpy(shard(order, step)).to(device)]
-            want = (step % args.log_every == 0) or step == steps_per_epoch - 1
-            m = trainer.step(batch, n_global=gb, keep_latent=(step == 0), want_metrics=True)
-            total += m["loss"]
-            if want:
-                last = m
-        torch.cuda.synchronize(device)
-        dt = time.perf_counter() - t0
-        if (epoch + 1) % DEAD_CODE_RESET_INTERVAL == 0:
-            n_dead = trainer.reset_dead_codes()
-            if n_dead:
-                log(f"INFO: Resetting {n_dead} dead codes.")
-        val = {"recon_error": 0.0, "vq_loss": 0.0, "recon_mse": 0.0, "recon_l1": 0.0}
-        n_val = max(len(va_ids) // gb, 1)
-        vbatches = []
-        for step in range(n_val):
-            ids = shard(va_ids, step) if len(va_ids) >= gb else va_ids[rank::world]
-            vbatch = d_all[torch.from_numpy(ids).to(device)]
-            mv = trainer.evaluate(vbatch)
-            for k in val:
-                val[k] += mv[k] / n_val
-            if args.report_leaf_error:
-                vbatches.append(vbatch)
-        val_loss = val["recon_error"] + val["vq_loss"]
+    def extras(codec, vbatches, val):
+        rec, before, after = {}, [], []
         if args.eval_precision == "bf16":   # the same validation batches through encode / decode in bf16-operand mode
-            vb = {"recon_mse": 0.0, "recon_l1": 0.0}
+            mse = l1 = 0.0
             codec.precision = "bf16"
-            for step in range(n_val):
-                ids = shard(va_ids, step) if len(va_ids) >= gb else va_ids[rank::world]
-                for k, v in eval_roundtrip(codec, d_all[torch.from_numpy(ids).to(device)]).items():
-                    vb[k] += v / n_val
+            for vbatch in vbatches:
+                r = eval_roundtrip(codec, vbatch)
+                mse, l1 = mse + r["recon_mse"] / len(vbatches), l1 + r["recon_l1"] / len(vbatches)
             codec.precision = "fp32"
-            vb["recon_error"] = 0.8 * vb["recon_mse"] + 0.2 * vb["recon_l1"]
-        rec = {"epoch": epoch + 1, "train_loss": total / steps_per_epoch, "train_vq_loss": last["vq_loss"], "perplexity": last["perplexity"],
-               "codes_used": last["codes_used"], "val_loss": val_loss, **{f"val_{k}": v for k, v in val.items()},
-               "leaves_per_s": steps_per_epoch * gb / dt, "epoch_s": dt, "lr": last["lr"]}
-        if args.eval_precision == "bf16":
-            rec.update({f"val_bf16_{k}": v for k, v in vb.items()})
-            log(f"         | Val recon fp32: {val['recon_error']:.6f} | Val recon bf16 inference: {vb['recon_error']:.6f}")
-        history.append(rec)
-        log(f"Epoch {epoch + 1:02d}/{args.epochs} | Train Loss: {rec['train_loss']:.6f} | Val Loss: {val_loss:.6f} | "
-            f"Perplexity: {last['perplexity']:.2f} | {rec['leaves_per_s'] / 1e3:.1f} k leaves/s ({dt:.2f} s/epoch)")
+            rec = {"val_bf16_recon_mse": mse, "val_bf16_recon_l1": l1, "val_bf16_recon_error": 0.8 * mse + 0.2 * l1}
+            before.append(f"         | Val recon fp32: {val['recon_error']:.6f} | Val recon bf16 inference: {rec['val_bf16_recon_error']:.6f}")
         if args.report_leaf_error:
-            log(leaf_error_line(codec, vbatches))
-        if val_loss < best_val and rank == 0:
-            best_val = val_loss
-            np.savez(args.model_path, epoch=epoch + 1, best_val_loss=best_val, **trainer.checkpoint())
-            log(f"New best validation loss: {val_loss:.6f} - model saved.")
-    trainer.finish()
-    if rank == 0:
-        root, ext = os.path.splitext(args.model_path)
-        np.savez(root + "_final" + (ext or ".npz"), epoch=args.epochs, **trainer.checkpoint())
-        if args.export_pack:
-            export_pack(args.pack, trainer.state_dict(), root + "_final.vqw")
-            log(f"Vec3 weight pack with the trained model: {root}_final.vqw")
-    log("Training completed!")
-    codec.close()
-    return {"history": history, "best_val_loss": best_val, "steps_per_epoch": steps_per_epoch, "world": world}
+            after.append(leaf_error_line(codec, vbatches))
+        return rec, before, after
+
+    return run_training(args, SPEC, build, export=export if args.export_pack else None,
+                        after_validation=extras if args.eval_precision == "bf16" or args.report_leaf_error else None)
 
 
 def main(argv=None):
