@@ -122,6 +122,11 @@ VEC3_PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_VEC3_PRECISION_*
 VEC3_BOUNDED_SYMBOLS = ["vqhip_vec3_roundtrip_device", "vqhip_vec3_select_outliers_device", "vqhip_vec3_compress_bounded"]
 VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
 
+# every symbol include/vqvdb_hip_bounded.h declares (error-bounded compression on the scalar handle; kept apart from the lists above)
+BOUNDED_SYMBOLS = ["vqhip_roundtrip_device", "vqhip_select_outliers_device", "vqhip_compress_bounded", "vqhip_decompress_bounded",
+                   "vqhip_compress_file_bounded", "vqhip_decompress_file_bounded"]
+ERR_FLOATS = 2   # VQHIP_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
+
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
 
 
@@ -134,6 +139,14 @@ class StreamStats(ctypes.Structure):
     """vqhip_stream_stats: where a whole-file compress/decompress spent its time."""
     _fields_ = [("leaves", ctypes.c_int64), ("grids", ctypes.c_int32), ("wall_s", ctypes.c_double), ("read_s", ctypes.c_double),
                 ("alloc_s", ctypes.c_double), ("copy_s", ctypes.c_double), ("io_wait_s", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BoundedStats(ctypes.Structure):
+    """vqhip_bounded_stats: what a bounded whole-file compress kept and what it stored raw."""
+    _fields_ = [("leaves", ctypes.c_int64), ("outliers", ctypes.c_int64), ("max_err_kept", ctypes.c_float), ("sum_sq_kept", ctypes.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -267,6 +280,16 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_select_outliers_device.argtypes = [vp, vp, i64, cf, vp, vp, vp]
     lib.vqhip_vec3_compress_bounded.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp]
     for name in VEC3_BOUNDED_SYMBOLS:
+        getattr(lib, name).restype = ci
+    # include/vqvdb_hip_bounded.h
+    lib.vqhip_roundtrip_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.vqhip_select_outliers_device.argtypes = [vp, vp, i64, cf, vp, vp, vp]
+    lib.vqhip_compress_bounded.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp]
+    lib.vqhip_decompress_bounded.argtypes = [vp, vp, i64, vp, i64, vp, vp]
+    lib.vqhip_compress_file_bounded.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_GridSource), ci, i64, cf,
+                                                ctypes.POINTER(StreamStats), ctypes.POINTER(BoundedStats)]
+    lib.vqhip_decompress_file_bounded.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, i64, GRID_BEGIN_FN, LEAF_ALLOC_FN, vp, ctypes.POINTER(StreamStats)]
+    for name in BOUNDED_SYMBOLS:
         getattr(lib, name).restype = ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
@@ -712,6 +735,13 @@ class HipCodec:
     def compress_file(self, path, grids, batch_leaves: int = 0) -> dict:
         """Whole-file compress (vqhip_compress_file).  grids: sequence of (name, origins int32 [n,3], leaves float32 [n,512]
         or a list of n 512-float arrays, transform or None).  Returns the stream statistics."""
+        src, n_g, _keep = self._grid_sources(grids)
+        st = StreamStats()
+        self._check(self._lib.vqhip_compress_file(self._h, os.fspath(path).encode(), src, n_g, batch_leaves, ctypes.byref(st)))
+        return st.as_dict()
+
+    def _grid_sources(self, grids):
+        """(vqhip_grid_source array, its length, the arrays it points into) of compress_file's grid tuples."""
         n_g = len(grids)
         src = (_GridSource * max(n_g, 1))()
         keep = []
@@ -735,15 +765,16 @@ class HipCodec:
             src[i].leaf_ptrs = ptrs.ctypes.data if n else None
             src[i].origins = origins.ctypes.data if n else None
             src[i].n_leaves = n
-        st = StreamStats()
-        self._check(self._lib.vqhip_compress_file(self._h, os.fspath(path).encode(), src, n_g, batch_leaves, ctypes.byref(st)))
-        return st.as_dict()
+        return src, n_g, keep
 
     def decompress_file(self, path, batch_leaves: int = 0, out: Optional[np.ndarray] = None):
         """Whole-file decompress (vqhip_decompress_file).  Returns ([(name, transform[16], origins [n,3], leaves [n,512])], stats);
         the leaf allocator hands out one fresh 2 KiB-per-leaf block per batch, the stand-in for tree.touchLeaf().
         out: optional preallocated C-contiguous float32 [total_leaves, 512] pool — leaves of all grids are then placed in it in
         file order (no per-batch allocation, no concatenation: multi-million-leaf files) and the returned leaf arrays are views."""
+        return self._decompress_file(path, None, batch_leaves, out)
+
+    def _decompress_file(self, path, residual_path, batch_leaves, out):
         grids, blocks = [], []
         if out is not None and (out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != LEAF_VOXELS or not out.flags.c_contiguous):
             raise ValueError("out must be a C-contiguous float32 [n, 512] array")
@@ -775,7 +806,11 @@ class HipCodec:
 
         cb_g, cb_a = GRID_BEGIN_FN(on_grid), LEAF_ALLOC_FN(on_alloc)
         st = StreamStats()
-        self._check(self._lib.vqhip_decompress_file(self._h, os.fspath(path).encode(), batch_leaves, cb_g, cb_a, None, ctypes.byref(st)))
+        if residual_path is None:
+            self._check(self._lib.vqhip_decompress_file(self._h, os.fspath(path).encode(), batch_leaves, cb_g, cb_a, None, ctypes.byref(st)))
+        else:
+            self._check(self._lib.vqhip_decompress_file_bounded(self._h, os.fspath(path).encode(), os.fspath(residual_path).encode(), batch_leaves,
+                                                                cb_g, cb_a, None, ctypes.byref(st)))
         result = []
         for (name, tr, _total), bl in zip(grids, blocks):
             org = np.concatenate([b[0] for b in bl]) if bl else np.zeros((0, 3), np.int32)
@@ -795,6 +830,142 @@ class HipCodec:
 
     def set_chunk_leaves(self, n: int):
         self._check(self._lib.vqhip_set_chunk_leaves(self._h, n))
+
+    # ---- error-bounded compression: include/vqvdb_hip_bounded.h ----
+    check_tol = staticmethod(HipVec3Codec.check_tol)
+
+    @classmethod
+    def check_bound(cls, tol) -> float:
+        """check_tol, and a tolerance below zero is refused: no error is <= it, so it can only be a mistake."""
+        t = cls.check_tol(tol)
+        if t < 0:
+            raise ValueError(f"tol must be >= 0 (or NaN: every leaf raw), got {tol!r}")
+        return t
+
+    @staticmethod
+    def check_leaves(leaves) -> np.ndarray:
+        """float32, C-contiguous, [n,512] or [n,8,8,8] -> [n,512] view."""
+        if not isinstance(leaves, np.ndarray) or leaves.dtype != np.float32:
+            raise TypeError("leaves must be a float32 numpy array")
+        if not leaves.flags.c_contiguous:
+            raise ValueError("leaves must be C-contiguous")
+        if leaves.ndim == 2 and leaves.shape[1] == LEAF_VOXELS:
+            return leaves
+        if leaves.ndim == 4 and leaves.shape[1:] == (8, 8, 8):
+            return leaves.reshape(-1, LEAF_VOXELS)
+        raise ValueError(f"leaves must have shape [n,512] or [n,8,8,8], got {list(leaves.shape)}")
+
+    @staticmethod
+    def check_indices(indices) -> np.ndarray:
+        """uint8, C-contiguous, [n,64] or [n,4,4,4] -> [n,64] view."""
+        if not isinstance(indices, np.ndarray) or indices.dtype != np.uint8:
+            raise TypeError("indices must be a uint8 numpy array")
+        if not indices.flags.c_contiguous:
+            raise ValueError("indices must be C-contiguous")
+        if indices.ndim == 2 and indices.shape[1] == LATENT_VOXELS:
+            return indices
+        if indices.ndim == 4 and indices.shape[1:] == (4, 4, 4):
+            return indices.reshape(-1, LATENT_VOXELS)
+        raise ValueError(f"indices must have shape [n,64] or [n,4,4,4], got {list(indices.shape)}")
+
+    @staticmethod
+    def check_outliers(n: int, outlier_ids, outlier_leaves):
+        """-> (ids int64 [m], raw float32 [m,512]): one raw leaf per id, the ids ascending, unique and in [0, n)."""
+        ids = np.asarray(outlier_ids)
+        if ids.size and not np.issubdtype(ids.dtype, np.integer):
+            raise TypeError("outlier ids must be integers")
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        raw = np.asarray(outlier_leaves)
+        if raw.size and raw.dtype != np.float32:
+            raise TypeError("outlier leaves must be float32")
+        if raw.size % LEAF_VOXELS:
+            raise ValueError("outlier leaves must hold 512 values each")
+        raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1, LEAF_VOXELS)
+        if len(ids) != len(raw):
+            raise ValueError(f"{len(ids)} outlier ids but {len(raw)} outlier leaves")
+        if len(ids) and (ids.min() < 0 or ids.max() >= n):
+            raise ValueError(f"outlier ids must be in [0, {n})")
+        if (np.diff(ids) <= 0).any():
+            raise ValueError("outlier ids must be ascending and unique")
+        return ids, raw
+
+    def roundtrip_device(self, leaves_ptr: int, n: int, leaf_err_ptr: int, idx_ptr: int = 0, recon_ptr: int = 0, stream: int = 0):
+        if not leaf_err_ptr:
+            raise ValueError("leaf_err_ptr is NULL: the leaf errors need a device buffer of n * 2 float32")
+        self._check(self._lib.vqhip_roundtrip_device(self._h, leaves_ptr, n, idx_ptr or None, recon_ptr or None, leaf_err_ptr, stream or None))
+
+    def select_outliers_device(self, leaf_err_ptr: int, n: int, tol: float, ids_ptr: int, count_ptr: int, stream: int = 0):
+        if not count_ptr:
+            raise ValueError("count_ptr is NULL: the count needs a device buffer of one int64")
+        self._check(self._lib.vqhip_select_outliers_device(self._h, leaf_err_ptr, n, self.check_tol(tol), ids_ptr, count_ptr, stream or None))
+
+    def _compress_bounded_host(self, leaves: np.ndarray, tol: float):
+        n = leaves.shape[0]
+        idx, err = np.empty((n, LATENT_VOXELS), dtype=np.uint8), np.empty((n, ERR_FLOATS), dtype=np.float32)
+        ids, count = np.empty(n, dtype=np.int64), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_compress_bounded(self._h, leaves.ctypes.data, n, tol, idx.ctypes.data, err.ctypes.data, ids.ctypes.data,
+                                                     ctypes.byref(count)))
+        return idx, err, ids[:count.value].copy()
+
+    def _decompress_bounded_host(self, indices: np.ndarray, ids: np.ndarray, raw: np.ndarray) -> np.ndarray:
+        out = np.empty((indices.shape[0], LEAF_VOXELS), dtype=np.float32)
+        self._check(self._lib.vqhip_decompress_bounded(self._h, indices.ctypes.data, indices.shape[0], ids.ctypes.data, len(ids), raw.ctypes.data,
+                                                       out.ctypes.data))
+        return out
+
+    def roundtrip(self, leaves, return_recon: bool = False):
+        """Encode and decode in one pass -> (indices [n,64], leaf_err [n,2] = per leaf max |x - x^| and sum (x - x^)^2
+        [, recon [n,512]]).  A float32 torch tensor on the handle's device gives device tensors, ordered on torch's current
+        stream (complete on return where that is the default stream); a numpy array goes through the host entry points."""
+        if isinstance(leaves, np.ndarray):
+            leaves = self.check_leaves(leaves)
+            idx, err, _ = self._compress_bounded_host(leaves, float("inf"))
+            return (idx, err, self.decode(idx)) if return_recon else (idx, err)
+        import torch
+        if not (isinstance(leaves, torch.Tensor) and leaves.is_cuda and leaves.dtype == torch.float32 and leaves.is_contiguous()):
+            raise TypeError("leaves must be a float32 numpy array or a contiguous float32 torch tensor on the GPU")
+        if tuple(leaves.shape[1:]) not in ((512,), (8, 8, 8)):
+            raise ValueError(f"leaves must have shape [n,512] or [n,8,8,8], got {list(leaves.shape)}")
+        n = leaves.shape[0]
+        idx = torch.empty((n, LATENT_VOXELS), dtype=torch.uint8, device=leaves.device)
+        err = torch.empty((n, ERR_FLOATS), dtype=torch.float32, device=leaves.device)
+        rec = torch.empty((n, LEAF_VOXELS), dtype=torch.float32, device=leaves.device) if return_recon else None
+        st = torch.cuda.current_stream(leaves.device).cuda_stream
+        if st == 0:   # a null handle means the codec's own stream: order it after the producer of `leaves` by hand
+            torch.cuda.synchronize(leaves.device)
+        self.roundtrip_device(leaves.data_ptr(), n, err.data_ptr(), idx.data_ptr(), rec.data_ptr() if return_recon else 0, st)
+        if st == 0:
+            torch.cuda.synchronize(leaves.device)
+        return (idx, err, rec) if return_recon else (idx, err)
+
+    def compress_bounded(self, leaves: np.ndarray, tol: float, return_leaf_err: bool = False):
+        """-> (indices [n,64], outlier_ids int64 ascending, outlier_leaves [m,512]): the leaves whose largest error is over
+        ``tol`` (or not finite) come back as raw copies, so that decompress_bounded stays within tol on every value."""
+        leaves = self.check_leaves(leaves)
+        idx, err, ids = self._compress_bounded_host(leaves, self.check_bound(tol))
+        out = (idx, ids, leaves[ids].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def decompress_bounded(self, indices: np.ndarray, outlier_ids, outlier_leaves) -> np.ndarray:
+        """Decoded leaves [n,512] with the leaves ``outlier_ids`` overwritten by their raw copies."""
+        indices = self.check_indices(indices)
+        ids, raw = self.check_outliers(indices.shape[0], outlier_ids, outlier_leaves)
+        return self._decompress_bounded_host(indices, ids, raw)
+
+    def compress_file_bounded(self, path, residual_path, grids, tol: float, batch_leaves: int = 0):
+        """compress_file with a tolerance (vqhip_compress_file_bounded): the same .vqvdb bytes, and the leaves over ``tol`` raw
+        in the .vqres sidecar ``residual_path`` (vqvdbfile.loads_residual reads it).  Returns (stream statistics, bounded
+        statistics: leaves, outliers, max_err_kept, sum_sq_kept)."""
+        tol = self.check_bound(tol)
+        src, n_g, _keep = self._grid_sources(grids)
+        st, bst = StreamStats(), BoundedStats()
+        self._check(self._lib.vqhip_compress_file_bounded(self._h, os.fspath(path).encode(), os.fspath(residual_path).encode(), src, n_g, batch_leaves,
+                                                          tol, ctypes.byref(st), ctypes.byref(bst)))
+        return st.as_dict(), bst.as_dict()
+
+    def decompress_file_bounded(self, path, residual_path, batch_leaves: int = 0, out: Optional[np.ndarray] = None):
+        """decompress_file, then the leaves the sidecar names are overwritten with its floats (vqhip_decompress_file_bounded)."""
+        return self._decompress_file(path, residual_path, batch_leaves, out)
 
     # ---- codebook training (VectorQuantizerEMA in training mode; see vqvdb_amd/codebook_training.py) ----
     def train_begin(self, cluster_size: Optional[np.ndarray] = None, embed_avg: Optional[np.ndarray] = None):

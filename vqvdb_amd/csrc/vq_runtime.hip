@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/vqvdb_hip.h"
+#include "../../include/vqvdb_hip_bounded.h"
 #include "vq_kernels.h"
 #include "vq_conv8_lds.h"
 #include "vq_stem_taps.h"
@@ -271,6 +272,20 @@ struct vqhip_codec {
     float* tr_recon = nullptr;  // reconstruction scratch of vqhip_train_eval_device
     int64_t tr_recon_leaves = 0;
     double* tr_loss_part = nullptr;
+    // error-bounded calls (vq_bounded.inc): every buffer lazy, sized to the largest chunk seen, freed in vqhip_destroy
+    float* bd_recon = nullptr;      // a chunk's reconstruction when the caller wants none stored
+    int64_t bd_recon_leaves = 0;
+    uint8_t* bd_idx = nullptr;      // a chunk's indices when the caller wants none
+    int64_t bd_idx_leaves = 0;
+    float* bd_err[2] = {nullptr, nullptr};       // leaf errors of the host calls, one per I/O slot ...
+    float* bd_pin_err[2] = {nullptr, nullptr};   // ... and their pinned landing zones
+    int64_t bd_err_leaves = 0;
+    int64_t* bd_ids = nullptr;      // outlier ids of one chunk, the count behind them
+    int64_t bd_ids_n = 0;
+    int64_t* bd_scan = nullptr;     // block counts / offsets of the selection
+    int64_t bd_scan_n = 0;
+    bool bd_pipe = false;           // run_pipeline: every encoded chunk is also decoded and measured (vqhip_compress_file_bounded)
+    const float* bd_pin_cur = nullptr;   // ... the leaf errors of the chunk being consumed
 };
 
 namespace {
@@ -1649,6 +1664,11 @@ int ensure_tables(vqhip_codec* c)
 using ProduceFn = std::function<const void*(int64_t, int64_t, void*)>;
 using ConsumeFn = std::function<int(int64_t, int64_t, const void*)>;
 
+// vq_bounded.inc: with c->bd_pipe set, an encoding pipeline also decodes every chunk and measures its leaves; consume()
+// then finds the chunk's leaf errors at c->bd_pin_cur
+int bd_ensure_pipe(vqhip_codec* c, int64_t m);
+int bd_pipe_chunk(vqhip_codec* c, const float* d_leaves, const uint8_t* d_idx, int64_t m, int slot, hipStream_t s);
+
 int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool want_stage, const ProduceFn& produce, const ConsumeFn& consume)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -1666,6 +1686,8 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
     if (rc) return rc;
     const size_t in_b = is_encode ? 2048 : 64, out_b = is_encode ? 64 : 2048;
     if (want_stage && (rc = ensure_stage(c, (size_t)step * in_b))) return rc;
+    const bool bounded = is_encode && c->bd_pipe;
+    if (bounded && (rc = bd_ensure_pipe(c, step))) return rc;
     if (n <= step) {
         // One chunk: there is nothing to overlap — H2D, kernels and D2H go down the compute stream in order and the call waits once.
         // (The three-stream form below costs such a call three cross-stream event hand-overs and as many extra API calls: the SOP's
@@ -1681,11 +1703,14 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         hipError_t e = hipMemcpyAsync(d_in, src, (size_t)n * in_b, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) return sync_fail(fail(c, VQHIP_ERR_DEVICE, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e)));
         rc = is_encode ? encode_chunk(c, c->dev_leaves[0], n, c->dev_idx[0], c->stream) : decode_chunk(c, c->dev_idx[0], n, c->dev_leaves[0], c->stream);
+        if (!rc && bounded) rc = bd_pipe_chunk(c, c->dev_leaves[0], c->dev_idx[0], n, 0, c->stream);
         if (rc) return sync_fail(rc);
         e = hipMemcpyAsync(c->pin_out[0], d_out, (size_t)n * out_b, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && bounded) e = hipMemcpyAsync(c->bd_pin_err[0], c->bd_err[0], (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) return sync_fail(fail(c, VQHIP_ERR_DEVICE, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e)));
         e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(c, VQHIP_ERR_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+        c->bd_pin_cur = c->bd_pin_err[0];
         return consume(0, n, c->pin_out[0]);
     }
     int64_t prev_off = -1, prev_m = 0;
@@ -1695,6 +1720,7 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         HIPCHK(c, hipEventSynchronize(c->ev_out[prev_slot]));
         const int64_t o = prev_off;
         prev_off = -1;
+        c->bd_pin_cur = c->bd_pin_err[prev_slot];
         return consume(o, prev_m, c->pin_out[prev_slot]);
     };
     auto abort_run = [&](int code) {  // leave no work in flight that still references caller memory
@@ -1727,11 +1753,13 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         if (i >= 2) PIPECHK(hipStreamWaitEvent(c->stream, c->ev_out[slot], 0));  // slot's previous output drained to pinned
         rc = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream)
                        : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream);
+        if (!rc && bounded) rc = bd_pipe_chunk(c, c->dev_leaves[slot], c->dev_idx[slot], m, slot, c->stream);
         if (rc) return abort_run(rc);
         PIPECHK(hipEventRecord(c->ev_done[slot], c->stream));
         if ((rc = drain())) return abort_run(rc);  // chunk i-1 -> caller, overlapped with chunk i on the GPU
         PIPECHK(hipStreamWaitEvent(c->s_out, c->ev_done[slot], 0));
         PIPECHK(hipMemcpyAsync(c->pin_out[slot], d_out, (size_t)m * out_b, hipMemcpyDeviceToHost, c->s_out));
+        if (bounded) PIPECHK(hipMemcpyAsync(c->bd_pin_err[slot], c->bd_err[slot], (size_t)m * 2 * sizeof(float), hipMemcpyDeviceToHost, c->s_out));
         PIPECHK(hipEventRecord(c->ev_out[slot], c->s_out));
         prev_off = o, prev_m = m, prev_slot = slot;
     }
@@ -1923,7 +1951,13 @@ void vqhip_destroy(vqhip_codec* c)
     if (c->ft_red_shared) hipStreamDestroy(c->ft_red_shared);
     if (c->tr_recon) hipFree(c->tr_recon);
     if (c->tr_loss_part) hipFree(c->tr_loss_part);
+    if (c->bd_recon) hipFree(c->bd_recon);
+    if (c->bd_idx) hipFree(c->bd_idx);
+    if (c->bd_ids) hipFree(c->bd_ids);
+    if (c->bd_scan) hipFree(c->bd_scan);
     for (int i = 0; i < 2; ++i) {
+        if (c->bd_err[i]) hipFree(c->bd_err[i]);
+        if (c->bd_pin_err[i]) hipHostFree(c->bd_pin_err[i]);
         if (c->dev_leaves[i]) hipFree(c->dev_leaves[i]);
         if (c->dev_idx[i]) hipFree(c->dev_idx[i]);
         if (c->pin_out[i]) hipHostFree(c->pin_out[i]);
@@ -2047,11 +2081,12 @@ int vqhip_decode_leaves(vqhip_codec* c, const uint8_t* indices, int64_t n, float
 // Replaces the body of VQVAECodec::decompress (VQVAECodec.cpp:137-208): per grid, a reader thread reads and de-frames
 // batch k+1..k+2 and asks the caller's allocator for their leaf buffers while the GPU decodes batch k and the calling
 // thread scatters batch k-1 straight from pinned memory into those buffers.
-int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin, vqhip_leaf_alloc_fn leaf_alloc,
-                          void* user, vqhip_stream_stats* stats)
+//
+// residual_path (vqhip_decompress_file_bounded, NULL otherwise): a .vqres sidecar (vqvdb_hip_bounded.h) read in step with the
+// batches; after a batch's scatter the leaves it names are overwritten with its floats.
+static int decompress_file_impl(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
+                                vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats)
 {
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file: null path or leaf allocator");
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open input file: ") + path);
     FileCloser closer{f};
@@ -2066,6 +2101,19 @@ int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves
     uint32_t num_emb;
     std::memcpy(&num_emb, h + 7, 4);
     if (dim_count != 3) return fail(c, VQHIP_ERR_INVALID, "latent rank " + std::to_string(dim_count) + " in file; this codec decodes [4,4,4] latents");
+    FILE* fr = nullptr;
+    if (residual_path) {
+        if (!(fr = std::fopen(residual_path, "rb"))) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open residual file: ") + residual_path);
+    }
+    FileCloser rcloser{fr};
+    if (fr) {
+        unsigned char rh[11];
+        if (std::fread(rh, 1, 11, fr) != 11) return fail(c, VQHIP_ERR_INVALID, "Failed to read residual file header.");
+        if (std::memcmp(rh, "VQRES", 5) != 0) return fail(c, VQHIP_ERR_INVALID, "Invalid residual file magic; not a .vqres file.");
+        if (rh[5] != 1) return fail(c, VQHIP_ERR_INVALID, "Unsupported .vqres version " + std::to_string((int)rh[5]) + " (expected 1).");
+        if (rh[6] != n_grids)
+            return fail(c, VQHIP_ERR_INVALID, "residual file holds " + std::to_string((int)rh[6]) + " grids, the .vqvdb file " + std::to_string(n_grids));
+    }
 
     for (int g = 0; g < n_grids; ++g) {
         vqhip_grid_info gi;
@@ -2090,6 +2138,32 @@ int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves
         if (grid_begin && grid_begin(user, &gi) != 0) return fail(c, VQHIP_ERR_INVALID, "grid_begin callback failed for grid '" + name + "'");
         ++st.grids;
         const int64_t n = total;
+        // sidecar entries of this grid: res_left still to apply, res_next the record index already read (-1: none), res_prev the last applied
+        int64_t res_left = 0, res_next = -1, res_prev = -1;
+        if (fr) {
+            uint32_t n_out = 0;
+            if (std::fread(&n_out, 4, 1, fr) != 1) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: no outlier count for grid '" + name + "'.");
+            if ((int64_t)n_out > n)
+                return fail(c, VQHIP_ERR_INVALID, "residual file: grid '" + name + "' lists " + std::to_string(n_out) + " leaves, the grid has " + std::to_string(n));
+            res_left = n_out;
+        }
+        auto apply_residual = [&](int64_t o, int64_t m, float* const* ptrs) -> int {
+            while (res_left > 0) {
+                if (res_next < 0) {
+                    uint32_t ri = 0;
+                    if (std::fread(&ri, 4, 1, fr) != 1) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
+                    if ((int64_t)ri >= n)
+                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' of " + std::to_string(n) + " leaves");
+                    if ((int64_t)ri <= res_prev)
+                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' is not ascending");
+                    res_next = ri;
+                }
+                if (res_next >= o + m) break;   // a later batch's leaf (earlier ones were applied with their batch: res_next >= o)
+                if (std::fread(ptrs[res_next - o], 4, 512, fr) != 512) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
+                res_prev = res_next, res_next = -1, --res_left;
+            }
+            return VQHIP_OK;
+        };
         if (n == 0) continue;
         const int64_t step = std::min(batch_leaves > 0 ? std::min(batch_leaves, c->chunk) : c->chunk, n);
         const int64_t nb = (n + step - 1) / step;
@@ -2152,17 +2226,20 @@ int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves
                     c->err = herr;
                     return nullptr;
                 }
-                return slot[k % Q].idx.data();
+                return slot[k % Q].idx.data() + (o - k * step) * 64;   // run_pipeline may cut a batch into pieces (host_split)
             },
             [&](int64_t o, int64_t m, const void* res) -> int {
                 const int64_t k = o / step;
+                float* const* ptrs = slot[k % Q].ptrs.data() + (o - k * step);
                 const double t = now_s();
-                scatter_leaves(slot[k % Q].ptrs.data(), static_cast<const float*>(res), m);
+                scatter_leaves(ptrs, static_cast<const float*>(res), m);
+                const int rrc = fr ? apply_residual(o, m, ptrs) : VQHIP_OK;
                 copy_s += now_s() - t;
+                if (o + m < std::min(n, (k + 1) * step)) return rrc;   // a piece of the batch: its slot is still in use
                 std::lock_guard<std::mutex> lk(mu);
                 consumed = k + 1;
                 cv.notify_all();
-                return VQHIP_OK;
+                return rrc;
             });
         {
             std::lock_guard<std::mutex> lk(mu);
@@ -2179,12 +2256,31 @@ int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves
     return VQHIP_OK;
 }
 
-// Replaces the body of VQVAECodec::compress (VQVAECodec.cpp:78-134): gather the leaf buffers into pinned memory,
-// encode on the GPU, frame {origin, 64 indices} records and append them to the file while the next batch encodes.
-int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_source* grids, int n_grids, int64_t batch_leaves, vqhip_stream_stats* stats)
+int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin, vqhip_leaf_alloc_fn leaf_alloc,
+                          void* user, vqhip_stream_stats* stats)
 {
     if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file: null path or grid list");
+    if (!path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file: null path or leaf allocator");
+    return decompress_file_impl(c, path, nullptr, batch_leaves, grid_begin, leaf_alloc, user, stats);
+}
+
+int vqhip_decompress_file_bounded(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
+                                  vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (!path || !residual_path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file_bounded: null path, residual path or leaf allocator");
+    return decompress_file_impl(c, path, residual_path, batch_leaves, grid_begin, leaf_alloc, user, stats);
+}
+
+// Replaces the body of VQVAECodec::compress (VQVAECodec.cpp:78-134): gather the leaf buffers into pinned memory,
+// encode on the GPU, frame {origin, 64 indices} records and append them to the file while the next batch encodes.
+//
+// residual_path (vqhip_compress_file_bounded, NULL otherwise): every chunk is also decoded and measured (c->bd_pipe); the leaves
+// with !(max error <= tol) go raw, from the caller's leaf buffers, into a .vqres sidecar (vqvdb_hip_bounded.h).  The .vqvdb
+// bytes are the same either way.
+static int compress_file_impl(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
+                              int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats)
+{
     if (n_grids < 1 || n_grids > 255) return fail(c, VQHIP_ERR_INVALID, "compress_file: a .vqvdb file holds 1..255 grids");
     for (int g = 0; g < n_grids; ++g) {
         const vqhip_grid_source& G = grids[g];
@@ -2194,6 +2290,18 @@ int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_sourc
     FILE* f = std::fopen(path, "wb");
     if (!f) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open output file: ") + path);
     FileCloser closer{f};
+    FILE* fr = nullptr;
+    if (residual_path) {
+        if (!(fr = std::fopen(residual_path, "wb"))) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open residual file: ") + residual_path);
+    }
+    FileCloser rcloser{fr};
+    struct PipeFlag {   // the pipeline measures its chunks for as long as this call runs, whichever way it ends
+        vqhip_codec* c;
+        ~PipeFlag() { c->bd_pipe = false; }
+    } pipe_flag{c};
+    c->bd_pipe = fr != nullptr;
+    vqhip_bounded_stats bst;
+    std::memset(&bst, 0, sizeof bst);
     const double t_start = now_s();
     vqhip_stream_stats st;
     std::memset(&st, 0, sizeof st);
@@ -2201,6 +2309,18 @@ int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_sourc
     auto put = [&](const void* p, size_t n) {
         if (n && std::fwrite(p, 1, n, f) != n) wfail = true;
     };
+    bool rfail = false;
+    auto rput = [&](const void* p, size_t n) {
+        if (std::fwrite(p, 1, n, fr) != n) rfail = true;
+    };
+    if (fr) {
+        unsigned char rh[11];
+        std::memcpy(rh, "VQRES", 5);
+        rh[5] = 1;
+        rh[6] = (unsigned char)n_grids;
+        std::memcpy(rh + 7, &tol, 4);
+        rput(rh, 11);
+    }
     unsigned char h[12];
     std::memcpy(h, "VQVDB", 5);
     h[5] = 3;
@@ -2222,6 +2342,13 @@ int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_sourc
         put(&total, 4);
         ++st.grids;
         if (wfail) return fail(c, VQHIP_ERR_INVALID, "Failed to write to .vqvdb file.");
+        long count_pos = 0;
+        uint32_t grid_out = 0;   // the grid's outlier count: a placeholder now, patched in once the grid is done
+        if (fr) {
+            count_pos = std::ftell(fr);
+            rput(&grid_out, 4);
+            if (rfail || count_pos < 0) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
+        }
         if (G.n_leaves == 0) continue;
         double copy_s = 0, write_s = 0;
         const int rc = run_pipeline(
@@ -2242,18 +2369,61 @@ int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_sourc
                     std::memcpy(p + 12, idx + 64 * l, 64);
                 }
                 put(rec.data(), rec.size());
+                if (fr) {
+                    const float* e = c->bd_pin_cur;   // this chunk's {max |d|, sum d^2} per leaf
+                    for (int64_t l = 0; l < m; ++l) {
+                        if (!(e[2 * l] <= tol)) {
+                            const uint32_t ri = (uint32_t)(o + l);
+                            rput(&ri, 4);
+                            rput(G.leaf_ptrs[o + l], 2048);
+                            ++grid_out;
+                        } else {
+                            bst.max_err_kept = std::max(bst.max_err_kept, e[2 * l]);
+                            bst.sum_sq_kept += e[2 * l + 1];
+                        }
+                    }
+                }
                 write_s += now_s() - t;
+                if (rfail) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
                 return wfail ? fail(c, VQHIP_ERR_INVALID, "Failed to write to .vqvdb file.") : VQHIP_OK;
             });
         if (rc) return rc;
+        if (fr) {
+            if (std::fseek(fr, count_pos, SEEK_SET) != 0) rfail = true;
+            rput(&grid_out, 4);
+            if (std::fseek(fr, 0, SEEK_END) != 0) rfail = true;
+            if (rfail) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
+            bst.outliers += grid_out;
+        }
         st.leaves += G.n_leaves;
         st.copy_s += copy_s, st.read_s += write_s;
     }
     closer.f = nullptr;
     if (std::fclose(f) != 0) return fail(c, VQHIP_ERR_INVALID, "Error closing the output file.");
+    if (fr) {
+        rcloser.f = nullptr;
+        if (std::fclose(fr) != 0) return fail(c, VQHIP_ERR_INVALID, "Error closing the residual file.");
+    }
     st.wall_s = now_s() - t_start;
+    bst.leaves = st.leaves;
     if (stats) *stats = st;
+    if (bstats) *bstats = bst;
     return VQHIP_OK;
+}
+
+int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_source* grids, int n_grids, int64_t batch_leaves, vqhip_stream_stats* stats)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (!path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file: null path or grid list");
+    return compress_file_impl(c, path, nullptr, grids, n_grids, batch_leaves, 0.0f, stats, nullptr);
+}
+
+int vqhip_compress_file_bounded(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
+                                int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (!path || !residual_path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file_bounded: null path, residual path or grid list");
+    return compress_file_impl(c, path, residual_path, grids, n_grids, batch_leaves, tol, stats, bstats);
 }
 
 // ---- codebook training (stage 1): VectorQuantizerEMA.forward in training mode, VQVAE_v2.py:107-156 ----
@@ -2740,5 +2910,6 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_vec3.inc"
 #include "vq_vec3_bf16.inc"
 #include "vq_vec3_bounded.inc"
+#include "vq_bounded.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"

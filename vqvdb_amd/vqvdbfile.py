@@ -1,5 +1,6 @@
 """`.vqvdb` v3 container in numpy (byte layout: SURVEY.md App. B; reference writer/reader
-src/Utils/VQVDB_Reader.cpp:81-150,168-300).  Host-side framing only — no codec work happens here.
+src/Utils/VQVDB_Reader.cpp:81-150,168-300).  Host-side framing only — no codec work happens here.  The `.vqres` sidecar of
+an error-bounded compress is framed at the end of this file.
 
     file : "VQVDB" | u8 version=3 | u8 numGrids | u32 numEmbeddings | u8 latentDimCount
     grid : u32 nameLength | name | f32 transform[16] | u16 latentShape[latentDimCount] | u32 totalBlocks
@@ -82,3 +83,69 @@ def save(path, grids: List[Grid], num_embeddings: int = 256) -> None:
 def load(path) -> List[Grid]:
     with open(path, "rb") as f:
         return loads(f.read())
+
+
+# ---- `.vqres` v1: the raw leaves of an error-bounded compress, beside a .vqvdb (include/vqvdb_hip_bounded.h) ----
+#     file : "VQRES" | u8 version=1 | u8 numGrids | f32 tol
+#     grid : u32 nOutliers | nOutliers x { u32 record_index | f32 leaf[512] }      (grids in the .vqvdb's order)
+# record_index: the leaf's position among that grid's records, ascending.
+RES_MAGIC = b"VQRES"
+RES_VERSION = 1
+RES_ENTRY = np.dtype([("record_index", "<u4"), ("leaf", "<f4", (512,))])
+assert RES_ENTRY.itemsize == 2052
+
+
+def dumps_residual(tol: float, grids) -> bytes:
+    """grids: one (record_index [m], leaves float32 [m,512]) pair per grid of the .vqvdb, in its order."""
+    if not 1 <= len(grids) <= 255:
+        raise ValueError("a .vqres file holds 1..255 grids")
+    out = [RES_MAGIC + struct.pack("<BB", RES_VERSION, len(grids)) + np.float32(tol).astype("<f4").tobytes()]
+    for ids, leaves in grids:
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        leaves = np.asarray(leaves, dtype=np.float32).reshape(-1, 512)
+        if len(ids) != len(leaves):
+            raise ValueError(f"{len(ids)} record indices but {len(leaves)} leaves")
+        if len(ids) and (ids.min() < 0 or ids.max() >= 1 << 32 or (np.diff(ids) <= 0).any()):
+            raise ValueError("record indices must be ascending, unique and below 2^32")
+        ent = np.empty(len(ids), dtype=RES_ENTRY)
+        ent["record_index"] = ids
+        ent["leaf"] = leaves
+        out.append(struct.pack("<I", len(ids)) + ent.tobytes())
+    return b"".join(out)
+
+
+def loads_residual(buf: bytes):
+    """-> (tol, [(record_index int64 [m], leaves float32 [m,512]) per grid])."""
+    if len(buf) < 11:
+        raise ValueError("Failed to read residual file header.")
+    if buf[:5] != RES_MAGIC:
+        raise ValueError("Invalid residual file magic; not a .vqres file.")
+    version, n_grids = struct.unpack_from("<BB", buf, 5)
+    if version != RES_VERSION:
+        raise ValueError(f"Unsupported .vqres version {version} (expected {RES_VERSION}).")
+    tol = float(np.frombuffer(buf, dtype="<f4", count=1, offset=7)[0])
+    off, grids = 11, []
+    for _ in range(n_grids):
+        if off + 4 > len(buf):
+            raise ValueError("Residual file truncated: no outlier count.")
+        (m,) = struct.unpack_from("<I", buf, off); off += 4
+        if off + m * RES_ENTRY.itemsize > len(buf):
+            raise ValueError("Residual file truncated: incomplete leaf entry.")
+        ent = np.frombuffer(buf, dtype=RES_ENTRY, count=m, offset=off); off += m * RES_ENTRY.itemsize
+        ids = ent["record_index"].astype(np.int64)
+        if (np.diff(ids) <= 0).any():
+            raise ValueError("residual file: record indices are not ascending")
+        grids.append((ids, ent["leaf"].copy()))
+    if off != len(buf):
+        raise ValueError("Residual file holds bytes past its last grid.")
+    return tol, grids
+
+
+def save_residual(path, tol: float, grids) -> None:
+    with open(path, "wb") as f:
+        f.write(dumps_residual(tol, grids))
+
+
+def load_residual(path):
+    with open(path, "rb") as f:
+        return loads_residual(f.read())
