@@ -125,6 +125,10 @@ VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x
 # every symbol include/vqvdb_hip_bounded.h declares (error-bounded compression on the scalar handle; kept apart from the lists above)
 BOUNDED_SYMBOLS = ["vqhip_roundtrip_device", "vqhip_select_outliers_device", "vqhip_compress_bounded", "vqhip_decompress_bounded",
                    "vqhip_compress_file_bounded", "vqhip_decompress_file_bounded"]
+# every symbol include/vqvdb_hip_residual.h declares (quantised residuals of the scalar handle; kept apart from the lists above)
+RESIDUAL_SYMBOLS = ["vqhip_residual_encode_device", "vqhip_residual_apply_device", "vqhip_compress_residual", "vqhip_decompress_residual",
+                    "vqhip_compress_file_residual", "vqhip_decompress_file_residual"]
+RES_KEPT, RES_RAW = 254, 255   # VQHIP_RES_KEPT, VQHIP_RES_RAW
 ERR_FLOATS = 2   # VQHIP_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
@@ -147,6 +151,14 @@ class StreamStats(ctypes.Structure):
 class BoundedStats(ctypes.Structure):
     """vqhip_bounded_stats: what a bounded whole-file compress kept and what it stored raw."""
     _fields_ = [("leaves", ctypes.c_int64), ("outliers", ctypes.c_int64), ("max_err_kept", ctypes.c_float), ("sum_sq_kept", ctypes.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ResidualStats(ctypes.Structure):
+    """vqhip_residual_stats: how a residual whole-file compress stored the leaves it selected."""
+    _fields_ = [("quantised", ctypes.c_int64), ("raw", ctypes.c_int64), ("payload_bytes", ctypes.c_int64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -290,6 +302,16 @@ def load_library() -> ctypes.CDLL:
                                                 ctypes.POINTER(StreamStats), ctypes.POINTER(BoundedStats)]
     lib.vqhip_decompress_file_bounded.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, i64, GRID_BEGIN_FN, LEAF_ALLOC_FN, vp, ctypes.POINTER(StreamStats)]
     for name in BOUNDED_SYMBOLS:
+        getattr(lib, name).restype = ci
+    # include/vqvdb_hip_residual.h
+    lib.vqhip_residual_encode_device.argtypes = [vp, vp, vp, vp, i64, cf, vp, vp, vp, i64, vp]
+    lib.vqhip_residual_apply_device.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp]
+    lib.vqhip_compress_residual.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp, vp]
+    lib.vqhip_decompress_residual.argtypes = [vp, vp, i64, cf, vp, vp, i64, vp]
+    lib.vqhip_compress_file_residual.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_GridSource), ci, i64, cf,
+                                                 ctypes.POINTER(StreamStats), ctypes.POINTER(BoundedStats), ctypes.POINTER(ResidualStats)]
+    lib.vqhip_decompress_file_residual.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, i64, GRID_BEGIN_FN, LEAF_ALLOC_FN, vp, ctypes.POINTER(StreamStats)]
+    for name in RESIDUAL_SYMBOLS:
         getattr(lib, name).restype = ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
@@ -774,7 +796,7 @@ class HipCodec:
         file order (no per-batch allocation, no concatenation: multi-million-leaf files) and the returned leaf arrays are views."""
         return self._decompress_file(path, None, batch_leaves, out)
 
-    def _decompress_file(self, path, residual_path, batch_leaves, out):
+    def _decompress_file(self, path, residual_path, batch_leaves, out, residual_version: int = 1):
         grids, blocks = [], []
         if out is not None and (out.dtype != np.float32 or out.ndim != 2 or out.shape[1] != LEAF_VOXELS or not out.flags.c_contiguous):
             raise ValueError("out must be a C-contiguous float32 [n, 512] array")
@@ -809,8 +831,8 @@ class HipCodec:
         if residual_path is None:
             self._check(self._lib.vqhip_decompress_file(self._h, os.fspath(path).encode(), batch_leaves, cb_g, cb_a, None, ctypes.byref(st)))
         else:
-            self._check(self._lib.vqhip_decompress_file_bounded(self._h, os.fspath(path).encode(), os.fspath(residual_path).encode(), batch_leaves,
-                                                                cb_g, cb_a, None, ctypes.byref(st)))
+            call = self._lib.vqhip_decompress_file_residual if residual_version == 2 else self._lib.vqhip_decompress_file_bounded
+            self._check(call(self._h, os.fspath(path).encode(), os.fspath(residual_path).encode(), batch_leaves, cb_g, cb_a, None, ctypes.byref(st)))
         result = []
         for (name, tr, _total), bl in zip(grids, blocks):
             org = np.concatenate([b[0] for b in bl]) if bl else np.zeros((0, 3), np.int32)
@@ -966,6 +988,92 @@ class HipCodec:
     def decompress_file_bounded(self, path, residual_path, batch_leaves: int = 0, out: Optional[np.ndarray] = None):
         """decompress_file, then the leaves the sidecar names are overwritten with its floats (vqhip_decompress_file_bounded)."""
         return self._decompress_file(path, residual_path, batch_leaves, out)
+
+    # ---- quantised residuals: include/vqvdb_hip_residual.h (DESIGN.md §17) ----
+    @staticmethod
+    def residual_record_sizes(leaf_class: np.ndarray) -> np.ndarray:
+        """int64 [n]: the record bytes of every class (0 for kept leaves); classes outside 0..16, 254, 255 are refused."""
+        c = leaf_class.astype(np.int64)
+        if ((c > 16) & (c != RES_KEPT) & (c != RES_RAW)).any():
+            raise ValueError("leaf classes must be 0..16, 254 (kept) or 255 (raw)")
+        return np.where(c == RES_KEPT, 0, np.where(c == RES_RAW, 2048, 64 * c))
+
+    @classmethod
+    def check_residual(cls, n: int, leaf_class, payload):
+        """-> (class uint8 [n], payload uint8 [bytes]): one class per leaf, each 0..16, 254 or 255, and exactly their records."""
+        if not isinstance(leaf_class, np.ndarray) or leaf_class.dtype != np.uint8:
+            raise TypeError("leaf_class must be a uint8 numpy array")
+        lc = np.ascontiguousarray(leaf_class).reshape(-1)
+        if len(lc) != n:
+            raise ValueError(f"{n} leaves but {len(lc)} classes")
+        if isinstance(payload, (bytes, bytearray, memoryview)):
+            payload = np.frombuffer(payload, dtype=np.uint8)
+        if not isinstance(payload, np.ndarray) or payload.dtype != np.uint8:
+            raise TypeError("payload must be bytes or a uint8 numpy array")
+        pl = np.ascontiguousarray(payload).reshape(-1)
+        need = int(cls.residual_record_sizes(lc).sum())
+        if need != len(pl):
+            raise ValueError(f"the classes need {need} payload bytes, got {len(pl)}")
+        return lc, pl
+
+    def residual_encode_device(self, leaves_ptr: int, recon_ptr: int, leaf_err_ptr: int, n: int, tol: float, class_ptr: int, offsets_ptr: int,
+                               payload_ptr: int, payload_capacity: int, stream: int = 0):
+        """vqhip_residual_encode_device: classes [n] u8, offsets [n+1] int64 (offsets[n] = the payload's bytes) and the payload."""
+        if n > 0 and not (leaves_ptr and recon_ptr and leaf_err_ptr and class_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, leaf_err, class and offsets are required")
+        if payload_capacity < 0:
+            raise ValueError("payload_capacity must be >= 0")
+        tol = self.check_bound(tol)
+        self._check(self._lib.vqhip_residual_encode_device(self._h, leaves_ptr, recon_ptr, leaf_err_ptr, n, tol, class_ptr,
+                                                           offsets_ptr, payload_ptr or None, payload_capacity, stream or None))
+
+    def residual_apply_device(self, leaves_ptr: int, n: int, tol: float, class_ptr: int, offsets_ptr: int, payload_ptr: int, stream: int = 0):
+        """vqhip_residual_apply_device: the decoded leaves at leaves_ptr corrected in place.  The device arrays are trusted."""
+        if n > 0 and not (leaves_ptr and class_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, class and offsets are required")
+        tol = self.check_bound(tol)
+        self._check(self._lib.vqhip_residual_apply_device(self._h, leaves_ptr, n, tol, class_ptr, offsets_ptr, payload_ptr or None,
+                                                          stream or None))
+
+    def compress_residual(self, leaves: np.ndarray, tol: float, return_leaf_err: bool = False):
+        """-> (indices [n,64], leaf_class uint8 [n], payload uint8 [bytes]): a leaf whose largest error is within ``tol`` is kept
+        (class 254), any other is stored as its residual on a grid of 1.875 * tol in class x 64 bytes (class 0..16) or, where
+        that cannot keep it within tol, raw (class 255), so that decompress_residual stays within tol on every value."""
+        leaves = self.check_leaves(leaves)
+        tol = self.check_bound(tol)
+        n = leaves.shape[0]
+        idx, err = np.empty((n, LATENT_VOXELS), dtype=np.uint8), np.empty((n, ERR_FLOATS), dtype=np.float32)
+        lc, payload, nbytes = np.empty(n, dtype=np.uint8), np.empty(n * 2048, dtype=np.uint8), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_compress_residual(self._h, leaves.ctypes.data, n, tol, idx.ctypes.data, err.ctypes.data, lc.ctypes.data,
+                                                      payload.ctypes.data, ctypes.byref(nbytes)))
+        out = (idx, lc, payload[:nbytes.value].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def decompress_residual(self, indices: np.ndarray, tol: float, leaf_class, payload) -> np.ndarray:
+        """Decoded leaves [n,512] with the records of compress_residual (same ``tol``) applied."""
+        indices = self.check_indices(indices)
+        tol = self.check_bound(tol)
+        lc, pl = self.check_residual(indices.shape[0], leaf_class, payload)
+        out = np.empty((indices.shape[0], LEAF_VOXELS), dtype=np.float32)
+        self._check(self._lib.vqhip_decompress_residual(self._h, indices.ctypes.data, indices.shape[0], tol, lc.ctypes.data, pl.ctypes.data, len(pl),
+                                                        out.ctypes.data))
+        return out
+
+    def compress_file_residual(self, path, residual_path, grids, tol: float, batch_leaves: int = 0):
+        """compress_file with a tolerance and quantised records (vqhip_compress_file_residual): the same .vqvdb bytes, and the
+        records of the leaves over ``tol`` in the .vqres v2 sidecar ``residual_path`` (vqvdbfile.load_residual_v2 reads it).
+        Returns (stream statistics, bounded statistics with outliers = the selected leaves, residual statistics: quantised,
+        raw, payload_bytes)."""
+        tol = self.check_bound(tol)
+        src, n_g, _keep = self._grid_sources(grids)
+        st, bst, rst = StreamStats(), BoundedStats(), ResidualStats()
+        self._check(self._lib.vqhip_compress_file_residual(self._h, os.fspath(path).encode(), os.fspath(residual_path).encode(), src, n_g, batch_leaves,
+                                                           tol, ctypes.byref(st), ctypes.byref(bst), ctypes.byref(rst)))
+        return st.as_dict(), bst.as_dict(), rst.as_dict()
+
+    def decompress_file_residual(self, path, residual_path, batch_leaves: int = 0, out: Optional[np.ndarray] = None):
+        """decompress_file with the sidecar's records applied to every decoded batch on the GPU (vqhip_decompress_file_residual)."""
+        return self._decompress_file(path, residual_path, batch_leaves, out, residual_version=2)
 
     # ---- codebook training (VectorQuantizerEMA in training mode; see vqvdb_amd/codebook_training.py) ----
     def train_begin(self, cluster_size: Optional[np.ndarray] = None, embed_avg: Optional[np.ndarray] = None):

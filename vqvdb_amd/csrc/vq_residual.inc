@@ -1,0 +1,259 @@
+// vq_residual.inc — runtime of the scalar handle's quantised residuals (vqhip_residual_encode_device, _apply_device,
+// _compress_residual, _decompress_residual and the file pair; include/vqvdb_hip_residual.h, DESIGN.md §17).  Part of
+// vq_runtime.hip's translation unit, after vq_bounded.inc: the round trip and its leaf errors are that file's, unchanged; the
+// four kernels of vq_residual.h follow them.  The file pair runs compress_file_impl / decompress_file_impl of vq_runtime.hip,
+// whose pipeline calls rs_pipe_chunk and the handle's rs_decode_hook below.
+
+#include "../../include/vqvdb_hip_residual.h"
+#include "vq_residual.h"
+
+static_assert(VQHIP_RES_KEPT == vqr::CLASS_KEPT && VQHIP_RES_RAW == vqr::CLASS_RAW, "the header's classes are the kernels'");
+
+namespace {
+
+inline unsigned rs_grid(int64_t n)
+{
+    return (unsigned)((n + vqr::RES_WAVES - 1) / vqr::RES_WAVES);
+}
+
+inline bool rs_class_ok(int cls)
+{
+    return cls <= 16 || cls == VQHIP_RES_KEPT || cls == VQHIP_RES_RAW;
+}
+
+inline int64_t rs_record_size(int cls)
+{
+    return cls == VQHIP_RES_KEPT ? 0 : cls == VQHIP_RES_RAW ? 2048 : 64 * (int64_t)cls;
+}
+
+// class, scan, pack of n leaves: d_off[n] ends as the payload's size
+int rs_encode(vqhip_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, float tol, uint8_t* d_class, int64_t* d_off,
+              uint8_t* d_payload, int64_t capacity, hipStream_t s)
+{
+    Launcher L{c, s, n};
+    L.run("residual_class", [&] {
+        hipLaunchKernelGGL(vqr::resid_class_k, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, d_err, n, tol, d_class, d_off);
+    });
+    L.run("residual_scan", [&] { hipLaunchKernelGGL(vqr::resid_scan_k, dim3(1), dim3(1024), 0, s, d_off, n); });
+    L.run("residual_pack", [&] {
+        hipLaunchKernelGGL(vqr::resid_pack_k, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, n, tol, d_class, d_off, d_payload,
+                           capacity);
+    });
+    return L.rc;
+}
+
+int rs_apply(vqhip_codec* c, float* d_leaves, int64_t n, float tol, const uint8_t* d_class, const int64_t* d_off, const uint8_t* d_payload, hipStream_t s)
+{
+    Launcher L{c, s, n};
+    L.run("residual_apply", [&] {
+        hipLaunchKernelGGL(vqr::resid_apply_k, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, n, tol, d_class, d_off, d_payload);
+    });
+    return L.rc;
+}
+
+// per I/O slot the classes, offsets and payload of m leaves on the device; `pinned`: also a pinned block per slot that holds
+// {int64 total | m + 1 offsets | m * 2048 payload bytes | m classes} (the file pair's landing zone and upload staging)
+int rs_ensure(vqhip_codec* c, int64_t m, bool pinned)
+{
+    if (m > c->rs_leaves) {
+        HIPCHK(c, hipDeviceSynchronize());
+        for (int i = 0; i < 2; ++i) {
+            if (c->rs_class[i]) hipFree(c->rs_class[i]);
+            if (c->rs_off[i]) hipFree(c->rs_off[i]);
+            if (c->rs_payload[i]) hipFree(c->rs_payload[i]);
+            if (c->rs_pin[i]) hipHostFree(c->rs_pin[i]);
+            c->rs_class[i] = nullptr, c->rs_off[i] = nullptr, c->rs_payload[i] = nullptr, c->rs_pin[i] = nullptr;
+        }
+        c->rs_leaves = 0, c->rs_pin_leaves = 0;
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(c, hipMalloc(&c->rs_class[i], (size_t)m));
+            HIPCHK(c, hipMalloc(&c->rs_off[i], (size_t)(m + 1) * sizeof(int64_t)));
+            HIPCHK(c, hipMalloc(&c->rs_payload[i], (size_t)m * 2048));
+        }
+        c->rs_leaves = m;
+    }
+    if (pinned && c->rs_pin_leaves < c->rs_leaves) {
+        HIPCHK(c, hipDeviceSynchronize());
+        for (int i = 0; i < 2; ++i) {
+            if (c->rs_pin[i]) hipHostFree(c->rs_pin[i]);
+            c->rs_pin[i] = nullptr;
+        }
+        c->rs_pin_leaves = 0;
+        for (int i = 0; i < 2; ++i) HIPCHK(c, hipHostMalloc(&c->rs_pin[i], (size_t)c->rs_leaves * (8 + 2048 + 1) + 16, hipHostMallocDefault));
+        c->rs_pin_leaves = c->rs_leaves;
+    }
+    return VQHIP_OK;
+}
+
+int64_t* rs_pin_off(vqhip_codec* c, int slot) { return reinterpret_cast<int64_t*>(c->rs_pin[slot]) + 1; }
+unsigned char* rs_pin_payload(vqhip_codec* c, int slot) { return c->rs_pin[slot] + (size_t)(c->rs_pin_leaves + 2) * 8; }
+unsigned char* rs_pin_class(vqhip_codec* c, int slot) { return rs_pin_payload(c, slot) + (size_t)c->rs_pin_leaves * 2048; }
+
+// run_pipeline's encode step of a residual file compress, behind bd_pipe_chunk: the slot's chunk is measured; class, place, pack
+int rs_pipe_chunk(vqhip_codec* c, const float* d_leaves, int64_t m, int slot, hipStream_t s)
+{
+    return rs_encode(c, d_leaves, c->bd_recon, c->bd_err[slot], m, c->rs_tol, c->rs_class[slot], c->rs_off[slot], c->rs_payload[slot], m * 2048, s);
+}
+
+// ... and its classes and total on their way to pinned memory, behind the leaf errors on stream s
+hipError_t rs_pipe_copy_out(vqhip_codec* c, int64_t m, int slot, hipStream_t s)
+{
+    hipError_t e = hipMemcpyAsync(c->rs_pin[slot], c->rs_off[slot] + m, sizeof(int64_t), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(rs_pin_class(c, slot), c->rs_class[slot], (size_t)m, hipMemcpyDeviceToHost, s);
+    return e;
+}
+
+// the consumer of a residual file compress: the chunk's payload, now that its total is known.  The slot's device buffer is
+// not written again before the consumer returns, and stream c->rs_cur_stream is idle at this point.
+int rs_fetch_payload(vqhip_codec* c, int64_t m, const unsigned char** payload, int64_t* total)
+{
+    const int slot = c->rs_cur_slot;
+    std::memcpy(total, c->rs_pin[slot], sizeof(int64_t));
+    if (*total < 0 || *total > m * 2048) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: payload size out of range");
+    *payload = rs_pin_payload(c, slot);
+    if (*total == 0) return VQHIP_OK;
+    HIPCHK(c, hipMemcpyAsync(rs_pin_payload(c, slot), c->rs_payload[slot], (size_t)*total, hipMemcpyDeviceToHost, c->rs_cur_stream));
+    HIPCHK(c, hipStreamSynchronize(c->rs_cur_stream));
+    return VQHIP_OK;
+}
+
+// a residual file decompress: the slot's pinned block holds the chunk's classes and, in leaf order, its records; place them,
+// upload all three and apply them to the decoded chunk on stream s.  The block is not written again before that work is done.
+int rs_upload_apply(vqhip_codec* c, float* d_leaves, int64_t m, int slot, hipStream_t s)
+{
+    const unsigned char* cls = rs_pin_class(c, slot);
+    int64_t* off = rs_pin_off(c, slot);
+    off[0] = 0;
+    for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + rs_record_size(cls[i]);
+    const int64_t total = off[m];
+    HIPCHK(c, hipMemcpyAsync(c->rs_class[slot], rs_pin_class(c, slot), (size_t)m, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(c->rs_off[slot], rs_pin_off(c, slot), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    if (total > 0) HIPCHK(c, hipMemcpyAsync(c->rs_payload[slot], rs_pin_payload(c, slot), (size_t)total, hipMemcpyHostToDevice, s));
+    return rs_apply(c, d_leaves, m, c->rs_tol, c->rs_class[slot], c->rs_off[slot], c->rs_payload[slot], s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vqhip_residual_encode_device(vqhip_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, float tol, uint8_t* d_class,
+                                 int64_t* d_off, uint8_t* d_payload, int64_t capacity, void* stream)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0) return fail(c, VQHIP_ERR_INVALID, "residual_encode: n_leaves < 0");
+    if (n == 0) return VQHIP_OK;
+    if (capacity < 0) return fail(c, VQHIP_ERR_INVALID, "residual_encode: payload_capacity < 0");
+    if (!d_leaves || !d_recon || !d_err || !d_class || !d_off || (!d_payload && capacity > 0)) return fail(c, VQHIP_ERR_INVALID, "residual_encode: null pointer");
+    if (n > (int64_t(1) << 32)) return fail(c, VQHIP_ERR_INVALID, "residual_encode: n_leaves exceeds 2^32");
+    HIPCHK(c, hipSetDevice(c->device));
+    return rs_encode(c, d_leaves, d_recon, d_err, n, tol, d_class, d_off, d_payload, capacity, stream ? (hipStream_t)stream : c->stream);
+}
+
+int vqhip_residual_apply_device(vqhip_codec* c, float* d_leaves, int64_t n, float tol, const uint8_t* d_class, const int64_t* d_off,
+                                const uint8_t* d_payload, void* stream)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0) return fail(c, VQHIP_ERR_INVALID, "residual_apply: n_leaves < 0");
+    if (n == 0) return VQHIP_OK;
+    if (!d_leaves || !d_class || !d_off) return fail(c, VQHIP_ERR_INVALID, "residual_apply: null pointer");
+    if (n > (int64_t(1) << 32)) return fail(c, VQHIP_ERR_INVALID, "residual_apply: n_leaves exceeds 2^32");
+    HIPCHK(c, hipSetDevice(c->device));
+    return rs_apply(c, d_leaves, n, tol, d_class, d_off, d_payload, stream ? (hipStream_t)stream : c->stream);
+}
+
+int vqhip_compress_residual(vqhip_codec* c, const float* leaves, int64_t n, float tol, uint8_t* indices, float* leaf_err, uint8_t* leaf_class,
+                            uint8_t* payload, int64_t* payload_bytes)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0) return fail(c, VQHIP_ERR_INVALID, "compress_residual: n_leaves < 0");
+    if (!payload_bytes) return fail(c, VQHIP_ERR_INVALID, "compress_residual: payload_bytes is NULL");
+    *payload_bytes = 0;
+    if (n == 0) return VQHIP_OK;
+    if (!leaves || !indices || !leaf_class || !payload) return fail(c, VQHIP_ERR_INVALID, "compress_residual: null pointer");
+    if (int rc = bd_prepare(c)) return rc;
+    int64_t total = 0;
+    for (int64_t o = 0; o < n; o += c->chunk) {
+        const int64_t m = std::min(c->chunk, n - o);
+        if (int rc = ensure_io(c, m)) return rc;
+        if (int rc = bd_ensure_pipe(c, m)) return rc;
+        if (int rc = rs_ensure(c, m, false)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->dev_leaves[0], leaves + o * 512, (size_t)m * 2048, hipMemcpyHostToDevice, c->stream));
+        int rc = bd_roundtrip_chunk(c, c->dev_leaves[0], m, c->dev_idx[0], nullptr, c->bd_err[0], c->stream);
+        if (!rc) rc = rs_encode(c, c->dev_leaves[0], c->bd_recon, c->bd_err[0], m, tol, c->rs_class[0], c->rs_off[0], c->rs_payload[0], m * 2048, c->stream);
+        if (rc) {
+            hipStreamSynchronize(c->stream);   // the copy above may still read the caller's leaves
+            return rc;
+        }
+        HIPCHK(c, hipMemcpyAsync(indices + o * 64, c->dev_idx[0], (size_t)m * 64, hipMemcpyDeviceToHost, c->stream));
+        if (leaf_err)
+            HIPCHK(c, hipMemcpyAsync(leaf_err + o * VQHIP_ERR_FLOATS, c->bd_err[0], (size_t)m * VQHIP_ERR_FLOATS * sizeof(float), hipMemcpyDeviceToHost,
+                                     c->stream));
+        HIPCHK(c, hipMemcpyAsync(leaf_class + o, c->rs_class[0], (size_t)m, hipMemcpyDeviceToHost, c->stream));
+        int64_t bytes = 0;
+        HIPCHK(c, hipMemcpyAsync(&bytes, c->rs_off[0] + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bytes < 0 || bytes > m * 2048) return fail(c, VQHIP_ERR_DEVICE, "compress_residual: payload size out of range");
+        if (bytes > 0) HIPCHK(c, hipMemcpy(payload + total, c->rs_payload[0], (size_t)bytes, hipMemcpyDeviceToHost));
+        total += bytes;
+    }
+    *payload_bytes = total;
+    return VQHIP_OK;
+}
+
+int vqhip_decompress_residual(vqhip_codec* c, const uint8_t* indices, int64_t n, float tol, const uint8_t* leaf_class, const uint8_t* payload,
+                              int64_t payload_bytes, float* leaves)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0 || payload_bytes < 0) return fail(c, VQHIP_ERR_INVALID, "decompress_residual: n_leaves < 0 or payload_bytes < 0");
+    if (n == 0) return VQHIP_OK;
+    if (!indices || !leaves || !leaf_class || (payload_bytes > 0 && !payload)) return fail(c, VQHIP_ERR_INVALID, "decompress_residual: null pointer");
+    int64_t need = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!rs_class_ok(leaf_class[i]))
+            return fail(c, VQHIP_ERR_INVALID, "decompress_residual: class " + std::to_string((int)leaf_class[i]) + " of leaf " + std::to_string(i) +
+                                                  " is not 0..16, 254 or 255");
+        need += rs_record_size(leaf_class[i]);
+    }
+    if (need != payload_bytes)
+        return fail(c, VQHIP_ERR_INVALID, "decompress_residual: the classes need " + std::to_string(need) + " payload bytes, the caller gives " +
+                                              std::to_string(payload_bytes));
+    if (int rc = bd_prepare(c)) return rc;
+    std::vector<int64_t> off;
+    int64_t at = 0;
+    for (int64_t o = 0; o < n; o += c->chunk) {
+        const int64_t m = std::min(c->chunk, n - o);
+        if (int rc = ensure_io(c, m)) return rc;
+        if (int rc = rs_ensure(c, m, false)) return rc;
+        off.resize((size_t)m + 1);
+        off[0] = 0;
+        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + rs_record_size(leaf_class[o + i]);
+        HIPCHK(c, hipMemcpy(c->dev_idx[0], indices + o * 64, (size_t)m * 64, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->rs_class[0], leaf_class + o, (size_t)m, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->rs_off[0], off.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (off[m] > 0) HIPCHK(c, hipMemcpy(c->rs_payload[0], payload + at, (size_t)off[m], hipMemcpyHostToDevice));
+        at += off[m];
+        if (int rc = decode_chunk(c, c->dev_idx[0], m, c->dev_leaves[0], c->stream)) return rc;
+        if (int rc = rs_apply(c, c->dev_leaves[0], m, tol, c->rs_class[0], c->rs_off[0], c->rs_payload[0], c->stream)) return rc;
+        HIPCHK(c, hipMemcpyAsync(leaves + o * 512, c->dev_leaves[0], (size_t)m * 2048, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return VQHIP_OK;
+}
+
+int vqhip_compress_file_residual(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
+                                 int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats, vqhip_residual_stats* rstats)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (!path || !residual_path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file_residual: null path, residual path or grid list");
+    return compress_file_impl(c, path, residual_path, grids, n_grids, batch_leaves, tol, stats, bstats, 2, rstats);
+}
+
+int vqhip_decompress_file_residual(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
+                                   vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (!path || !residual_path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file_residual: null path, residual path or leaf allocator");
+    return decompress_file_impl(c, path, residual_path, batch_leaves, grid_begin, leaf_alloc, user, stats, 2);
+}
+
+}  // extern "C"

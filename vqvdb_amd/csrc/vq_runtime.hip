@@ -26,6 +26,7 @@
 
 #include "../../include/vqvdb_hip.h"
 #include "../../include/vqvdb_hip_bounded.h"
+#include "../../include/vqvdb_hip_residual.h"
 #include "vq_kernels.h"
 #include "vq_conv8_lds.h"
 #include "vq_stem_taps.h"
@@ -286,6 +287,19 @@ struct vqhip_codec {
     int64_t bd_scan_n = 0;
     bool bd_pipe = false;           // run_pipeline: every encoded chunk is also decoded and measured (vqhip_compress_file_bounded)
     const float* bd_pin_cur = nullptr;   // ... the leaf errors of the chunk being consumed
+    // quantised residuals (vq_residual.inc): lazy, sized to the largest chunk seen, freed in vqhip_destroy; one set per I/O slot
+    uint8_t* rs_class[2] = {nullptr, nullptr};
+    int64_t* rs_off[2] = {nullptr, nullptr};
+    uint8_t* rs_payload[2] = {nullptr, nullptr};
+    int64_t rs_leaves = 0;
+    unsigned char* rs_pin[2] = {nullptr, nullptr};   // the file pair's pinned block: total, offsets, payload, classes
+    int64_t rs_pin_leaves = 0;
+    bool rs_pipe = false;           // run_pipeline: every measured chunk is also classed, placed and packed (vqhip_compress_file_residual)
+    float rs_tol = 0.0f;            // ... at this tolerance
+    int rs_cur_slot = 0;            // ... the slot of the chunk being consumed and an idle stream for the consumer's payload fetch
+    hipStream_t rs_cur_stream = nullptr;
+    // run_pipeline: called behind every decoded chunk (offset, leaves, slot, the chunk on the device, its stream); vqhip_decompress_file_residual
+    std::function<int(int64_t, int64_t, int, float*, hipStream_t)> rs_decode_hook;
 };
 
 namespace {
@@ -1668,6 +1682,17 @@ using ConsumeFn = std::function<int(int64_t, int64_t, const void*)>;
 // then finds the chunk's leaf errors at c->bd_pin_cur
 int bd_ensure_pipe(vqhip_codec* c, int64_t m);
 int bd_pipe_chunk(vqhip_codec* c, const float* d_leaves, const uint8_t* d_idx, int64_t m, int slot, hipStream_t s);
+// vq_residual.inc: with c->rs_pipe set as well, the measured chunk is classed, placed and packed into the slot's payload buffer;
+// its classes and total travel behind the leaf errors, and consume() fetches the payload with rs_fetch_payload
+int rs_ensure(vqhip_codec* c, int64_t m, bool pinned);
+int rs_pipe_chunk(vqhip_codec* c, const float* d_leaves, int64_t m, int slot, hipStream_t s);
+hipError_t rs_pipe_copy_out(vqhip_codec* c, int64_t m, int slot, hipStream_t s);
+int rs_fetch_payload(vqhip_codec* c, int64_t m, const unsigned char** payload, int64_t* total);
+// ... and a decoding pipeline calls c->rs_decode_hook behind every decoded chunk; the hook stages the chunk's classes and records
+// in the slot's pinned block and hands them to rs_upload_apply
+unsigned char* rs_pin_class(vqhip_codec* c, int slot);
+unsigned char* rs_pin_payload(vqhip_codec* c, int slot);
+int rs_upload_apply(vqhip_codec* c, float* d_leaves, int64_t m, int slot, hipStream_t s);
 
 int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool want_stage, const ProduceFn& produce, const ConsumeFn& consume)
 {
@@ -1688,6 +1713,8 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
     if (want_stage && (rc = ensure_stage(c, (size_t)step * in_b))) return rc;
     const bool bounded = is_encode && c->bd_pipe;
     if (bounded && (rc = bd_ensure_pipe(c, step))) return rc;
+    const bool resid = bounded && c->rs_pipe;
+    if ((resid || (!is_encode && c->rs_decode_hook)) && (rc = rs_ensure(c, step, true))) return rc;
     if (n <= step) {
         // One chunk: there is nothing to overlap — H2D, kernels and D2H go down the compute stream in order and the call waits once.
         // (The three-stream form below costs such a call three cross-stream event hand-overs and as many extra API calls: the SOP's
@@ -1704,13 +1731,17 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         if (e != hipSuccess) return sync_fail(fail(c, VQHIP_ERR_DEVICE, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e)));
         rc = is_encode ? encode_chunk(c, c->dev_leaves[0], n, c->dev_idx[0], c->stream) : decode_chunk(c, c->dev_idx[0], n, c->dev_leaves[0], c->stream);
         if (!rc && bounded) rc = bd_pipe_chunk(c, c->dev_leaves[0], c->dev_idx[0], n, 0, c->stream);
+        if (!rc && resid) rc = rs_pipe_chunk(c, c->dev_leaves[0], n, 0, c->stream);
+        if (!rc && !is_encode && c->rs_decode_hook) rc = c->rs_decode_hook(0, n, 0, c->dev_leaves[0], c->stream);
         if (rc) return sync_fail(rc);
         e = hipMemcpyAsync(c->pin_out[0], d_out, (size_t)n * out_b, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess && bounded) e = hipMemcpyAsync(c->bd_pin_err[0], c->bd_err[0], (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && resid) e = rs_pipe_copy_out(c, n, 0, c->stream);
         if (e != hipSuccess) return sync_fail(fail(c, VQHIP_ERR_DEVICE, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e)));
         e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(c, VQHIP_ERR_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
         c->bd_pin_cur = c->bd_pin_err[0];
+        c->rs_cur_slot = 0, c->rs_cur_stream = c->stream;
         return consume(0, n, c->pin_out[0]);
     }
     int64_t prev_off = -1, prev_m = 0;
@@ -1721,6 +1752,7 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         const int64_t o = prev_off;
         prev_off = -1;
         c->bd_pin_cur = c->bd_pin_err[prev_slot];
+        c->rs_cur_slot = prev_slot, c->rs_cur_stream = c->s_out;   // s_out is idle here: the next chunk's copies are queued after this drain
         return consume(o, prev_m, c->pin_out[prev_slot]);
     };
     auto abort_run = [&](int code) {  // leave no work in flight that still references caller memory
@@ -1754,12 +1786,15 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         rc = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream)
                        : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream);
         if (!rc && bounded) rc = bd_pipe_chunk(c, c->dev_leaves[slot], c->dev_idx[slot], m, slot, c->stream);
+        if (!rc && resid) rc = rs_pipe_chunk(c, c->dev_leaves[slot], m, slot, c->stream);
+        if (!rc && !is_encode && c->rs_decode_hook) rc = c->rs_decode_hook(o, m, slot, c->dev_leaves[slot], c->stream);
         if (rc) return abort_run(rc);
         PIPECHK(hipEventRecord(c->ev_done[slot], c->stream));
         if ((rc = drain())) return abort_run(rc);  // chunk i-1 -> caller, overlapped with chunk i on the GPU
         PIPECHK(hipStreamWaitEvent(c->s_out, c->ev_done[slot], 0));
         PIPECHK(hipMemcpyAsync(c->pin_out[slot], d_out, (size_t)m * out_b, hipMemcpyDeviceToHost, c->s_out));
         if (bounded) PIPECHK(hipMemcpyAsync(c->bd_pin_err[slot], c->bd_err[slot], (size_t)m * 2 * sizeof(float), hipMemcpyDeviceToHost, c->s_out));
+        if (resid) PIPECHK(rs_pipe_copy_out(c, m, slot, c->s_out));
         PIPECHK(hipEventRecord(c->ev_out[slot], c->s_out));
         prev_off = o, prev_m = m, prev_slot = slot;
     }
@@ -1958,6 +1993,10 @@ void vqhip_destroy(vqhip_codec* c)
     for (int i = 0; i < 2; ++i) {
         if (c->bd_err[i]) hipFree(c->bd_err[i]);
         if (c->bd_pin_err[i]) hipHostFree(c->bd_pin_err[i]);
+        if (c->rs_class[i]) hipFree(c->rs_class[i]);
+        if (c->rs_off[i]) hipFree(c->rs_off[i]);
+        if (c->rs_payload[i]) hipFree(c->rs_payload[i]);
+        if (c->rs_pin[i]) hipHostFree(c->rs_pin[i]);
         if (c->dev_leaves[i]) hipFree(c->dev_leaves[i]);
         if (c->dev_idx[i]) hipFree(c->dev_idx[i]);
         if (c->pin_out[i]) hipHostFree(c->pin_out[i]);
@@ -2083,9 +2122,11 @@ int vqhip_decode_leaves(vqhip_codec* c, const uint8_t* indices, int64_t n, float
 // thread scatters batch k-1 straight from pinned memory into those buffers.
 //
 // residual_path (vqhip_decompress_file_bounded, NULL otherwise): a .vqres sidecar (vqvdb_hip_bounded.h) read in step with the
-// batches; after a batch's scatter the leaves it names are overwritten with its floats.
+// batches; after a batch's scatter the leaves it names are overwritten with its floats.  res_version 2
+// (vqhip_decompress_file_residual): a .vqres v2 sidecar (vqvdb_hip_residual.h); the records of a decoded batch are read forward,
+// uploaded and applied on the GPU before the batch leaves it.
 static int decompress_file_impl(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
-                                vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats)
+                                vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats, int res_version = 1)
 {
     FILE* f = std::fopen(path, "rb");
     if (!f) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open input file: ") + path);
@@ -2110,7 +2151,9 @@ static int decompress_file_impl(vqhip_codec* c, const char* path, const char* re
         unsigned char rh[11];
         if (std::fread(rh, 1, 11, fr) != 11) return fail(c, VQHIP_ERR_INVALID, "Failed to read residual file header.");
         if (std::memcmp(rh, "VQRES", 5) != 0) return fail(c, VQHIP_ERR_INVALID, "Invalid residual file magic; not a .vqres file.");
-        if (rh[5] != 1) return fail(c, VQHIP_ERR_INVALID, "Unsupported .vqres version " + std::to_string((int)rh[5]) + " (expected 1).");
+        if (rh[5] != res_version)
+            return fail(c, VQHIP_ERR_INVALID, "Unsupported .vqres version " + std::to_string((int)rh[5]) + " (expected " + std::to_string(res_version) + ").");
+        std::memcpy(&c->rs_tol, rh + 7, 4);
         if (rh[6] != n_grids)
             return fail(c, VQHIP_ERR_INVALID, "residual file holds " + std::to_string((int)rh[6]) + " grids, the .vqvdb file " + std::to_string(n_grids));
     }
@@ -2164,6 +2207,43 @@ static int decompress_file_impl(vqhip_codec* c, const char* path, const char* re
             }
             return VQHIP_OK;
         };
+        // v2: the same walk behind every decoded chunk, into the slot's pinned block; res_class is the class already read with res_next
+        int res_class = 0;
+        auto stage_residual = [&](int64_t o, int64_t m, int slot, float* d_leaves, hipStream_t s) -> int {
+            unsigned char* cls = rs_pin_class(c, slot);
+            unsigned char* pay = rs_pin_payload(c, slot);
+            bool any = false;
+            while (res_left > 0) {
+                if (res_next < 0) {
+                    unsigned char eh[5];
+                    uint32_t ri = 0;
+                    if (std::fread(eh, 1, 5, fr) != 5) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
+                    std::memcpy(&ri, eh, 4);
+                    if ((int64_t)ri >= n)
+                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' of " + std::to_string(n) + " leaves");
+                    if ((int64_t)ri <= res_prev)
+                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' is not ascending");
+                    if (eh[4] > 16 && eh[4] != VQHIP_RES_RAW)
+                        return fail(c, VQHIP_ERR_INVALID, "residual file: class " + std::to_string((int)eh[4]) + " of record " + std::to_string(ri) + " in grid '" + name +
+                                                              "' is not 0..16 or 255");
+                    res_next = ri, res_class = eh[4];
+                }
+                if (res_next >= o + m) break;   // a later chunk's leaf
+                if (!any) std::memset(cls, VQHIP_RES_KEPT, (size_t)m), any = true;
+                const size_t sz = res_class == VQHIP_RES_RAW ? 2048 : 64 * (size_t)res_class;
+                if (sz && std::fread(pay, 1, sz, fr) != sz) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
+                pay += sz;
+                cls[res_next - o] = (unsigned char)res_class;
+                res_prev = res_next, res_next = -1, --res_left;
+            }
+            return any ? rs_upload_apply(c, d_leaves, m, slot, s) : VQHIP_OK;
+        };
+        struct HookGuard {   // the pipeline applies records for as long as this grid's run lasts, whichever way it ends
+            vqhip_codec* c;
+            ~HookGuard() { c->rs_decode_hook = nullptr; }
+        } hook_guard{c};
+        const bool v2 = fr && res_version == 2;
+        if (v2) c->rs_decode_hook = stage_residual;
         if (n == 0) continue;
         const int64_t step = std::min(batch_leaves > 0 ? std::min(batch_leaves, c->chunk) : c->chunk, n);
         const int64_t nb = (n + step - 1) / step;
@@ -2233,7 +2313,7 @@ static int decompress_file_impl(vqhip_codec* c, const char* path, const char* re
                 float* const* ptrs = slot[k % Q].ptrs.data() + (o - k * step);
                 const double t = now_s();
                 scatter_leaves(ptrs, static_cast<const float*>(res), m);
-                const int rrc = fr ? apply_residual(o, m, ptrs) : VQHIP_OK;
+                const int rrc = fr && !v2 ? apply_residual(o, m, ptrs) : VQHIP_OK;
                 copy_s += now_s() - t;
                 if (o + m < std::min(n, (k + 1) * step)) return rrc;   // a piece of the batch: its slot is still in use
                 std::lock_guard<std::mutex> lk(mu);
@@ -2277,9 +2357,11 @@ int vqhip_decompress_file_bounded(vqhip_codec* c, const char* path, const char* 
 //
 // residual_path (vqhip_compress_file_bounded, NULL otherwise): every chunk is also decoded and measured (c->bd_pipe); the leaves
 // with !(max error <= tol) go raw, from the caller's leaf buffers, into a .vqres sidecar (vqvdb_hip_bounded.h).  The .vqvdb
-// bytes are the same either way.
+// bytes are the same either way.  res_version 2 (vqhip_compress_file_residual): the measured chunk is also classed and packed
+// (c->rs_pipe) and the sidecar holds each selected leaf's record, quantised or raw (.vqres v2, vqvdb_hip_residual.h).
 static int compress_file_impl(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
-                              int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats)
+                              int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats, int res_version = 1,
+                              vqhip_residual_stats* rstats = nullptr)
 {
     if (n_grids < 1 || n_grids > 255) return fail(c, VQHIP_ERR_INVALID, "compress_file: a .vqvdb file holds 1..255 grids");
     for (int g = 0; g < n_grids; ++g) {
@@ -2297,9 +2379,14 @@ static int compress_file_impl(vqhip_codec* c, const char* path, const char* resi
     FileCloser rcloser{fr};
     struct PipeFlag {   // the pipeline measures its chunks for as long as this call runs, whichever way it ends
         vqhip_codec* c;
-        ~PipeFlag() { c->bd_pipe = false; }
+        ~PipeFlag() { c->bd_pipe = false, c->rs_pipe = false; }
     } pipe_flag{c};
     c->bd_pipe = fr != nullptr;
+    const bool v2 = fr && res_version == 2;
+    c->rs_pipe = v2, c->rs_tol = tol;
+    vqhip_residual_stats rst;
+    std::memset(&rst, 0, sizeof rst);
+    std::vector<unsigned char> rrec;   // v2: a chunk's framed entries
     vqhip_bounded_stats bst;
     std::memset(&bst, 0, sizeof bst);
     const double t_start = now_s();
@@ -2316,7 +2403,7 @@ static int compress_file_impl(vqhip_codec* c, const char* path, const char* resi
     if (fr) {
         unsigned char rh[11];
         std::memcpy(rh, "VQRES", 5);
-        rh[5] = 1;
+        rh[5] = (unsigned char)res_version;
         rh[6] = (unsigned char)n_grids;
         std::memcpy(rh + 7, &tol, 4);
         rput(rh, 11);
@@ -2369,7 +2456,36 @@ static int compress_file_impl(vqhip_codec* c, const char* path, const char* resi
                     std::memcpy(p + 12, idx + 64 * l, 64);
                 }
                 put(rec.data(), rec.size());
-                if (fr) {
+                if (v2) {
+                    const float* e = c->bd_pin_cur;
+                    const unsigned char* pay = nullptr;
+                    int64_t pay_bytes = 0, at = 0;
+                    if (int frc = rs_fetch_payload(c, m, &pay, &pay_bytes)) return frc;
+                    const unsigned char* cls = pay + (size_t)c->rs_pin_leaves * 2048;   // the slot's classes lie behind its payload
+                    rrec.clear();
+                    for (int64_t l = 0; l < m; ++l) {
+                        if (cls[l] == VQHIP_RES_KEPT) {
+                            bst.max_err_kept = std::max(bst.max_err_kept, e[2 * l]);
+                            bst.sum_sq_kept += e[2 * l + 1];
+                            continue;
+                        }
+                        const int64_t sz = cls[l] == VQHIP_RES_RAW ? 2048 : 64 * (int64_t)cls[l];
+                        if (cls[l] > 16 && cls[l] != VQHIP_RES_RAW) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: class out of range");
+                        if (at + sz > pay_bytes) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: records exceed the payload");
+                        const uint32_t ri = (uint32_t)(o + l);
+                        const size_t w = rrec.size();
+                        rrec.resize(w + 5 + (size_t)sz);
+                        std::memcpy(&rrec[w], &ri, 4);
+                        rrec[w + 4] = cls[l];
+                        std::memcpy(&rrec[w + 5], pay + at, (size_t)sz);
+                        at += sz;
+                        ++grid_out;
+                        ++(cls[l] == VQHIP_RES_RAW ? rst.raw : rst.quantised);
+                    }
+                    if (at != pay_bytes) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: records do not fill the payload");
+                    rst.payload_bytes += pay_bytes;
+                    if (!rrec.empty()) rput(rrec.data(), rrec.size());
+                } else if (fr) {
                     const float* e = c->bd_pin_cur;   // this chunk's {max |d|, sum d^2} per leaf
                     for (int64_t l = 0; l < m; ++l) {
                         if (!(e[2 * l] <= tol)) {
@@ -2408,6 +2524,7 @@ static int compress_file_impl(vqhip_codec* c, const char* path, const char* resi
     bst.leaves = st.leaves;
     if (stats) *stats = st;
     if (bstats) *bstats = bst;
+    if (rstats) *rstats = rst;
     return VQHIP_OK;
 }
 
@@ -2911,5 +3028,6 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_vec3_bf16.inc"
 #include "vq_vec3_bounded.inc"
 #include "vq_bounded.inc"
+#include "vq_residual.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"

@@ -149,3 +149,85 @@ def save_residual(path, tol: float, grids) -> None:
 def load_residual(path):
     with open(path, "rb") as f:
         return loads_residual(f.read())
+
+
+# ---- `.vqres` v2: quantised or raw records of the leaves over the tolerance (include/vqvdb_hip_residual.h) ----
+#     file : "VQRES" | u8 version=2 | u8 numGrids | f32 tol
+#     grid : u32 nRecords | nRecords x { u32 record_index | u8 class | u8 bytes[class==255 ? 2048 : 64*class] }
+# record_index ascending within the grid; class 0 .. 16 (bit planes) or 255 (the leaf's 2048 bytes).
+RES_VERSION_2 = 2
+RES_CLASS_RAW = 255
+RES_CLASS_MAX_BITS = 16
+
+
+def residual_record_bytes(cls: int) -> int:
+    if cls == RES_CLASS_RAW:
+        return 2048
+    if 0 <= cls <= RES_CLASS_MAX_BITS:
+        return 64 * cls
+    raise ValueError(f"residual file: class {cls} is not 0..16 or 255")
+
+
+def dumps_residual_v2(tol: float, grids) -> bytes:
+    """grids: one (record_index [m], class [m], list of m record bytes) triple per grid of the .vqvdb, in its order."""
+    if not 1 <= len(grids) <= 255:
+        raise ValueError("a .vqres file holds 1..255 grids")
+    out = [RES_MAGIC + struct.pack("<BB", RES_VERSION_2, len(grids)) + np.float32(tol).astype("<f4").tobytes()]
+    for ids, classes, recs in grids:
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        classes = np.asarray(classes, dtype=np.int64).reshape(-1)
+        if not len(ids) == len(classes) == len(recs):
+            raise ValueError(f"{len(ids)} record indices, {len(classes)} classes and {len(recs)} records")
+        if len(ids) and (ids.min() < 0 or ids.max() >= 1 << 32 or (np.diff(ids) <= 0).any()):
+            raise ValueError("record indices must be ascending, unique and below 2^32")
+        out.append(struct.pack("<I", len(ids)))
+        for ri, cls, rec in zip(ids, classes, recs):
+            if len(rec) != residual_record_bytes(int(cls)):
+                raise ValueError(f"a record of class {int(cls)} holds {residual_record_bytes(int(cls))} bytes, not {len(rec)}")
+            out.append(struct.pack("<IB", int(ri), int(cls)) + bytes(rec))
+    return b"".join(out)
+
+
+def loads_residual_v2(buf: bytes):
+    """-> (tol, [(record_index int64 [m], class uint8 [m], list of m record bytes) per grid])."""
+    if len(buf) < 11:
+        raise ValueError("Failed to read residual file header.")
+    if buf[:5] != RES_MAGIC:
+        raise ValueError("Invalid residual file magic; not a .vqres file.")
+    version, n_grids = struct.unpack_from("<BB", buf, 5)
+    if version != RES_VERSION_2:
+        raise ValueError(f"Unsupported .vqres version {version} (expected {RES_VERSION_2}).")
+    tol = float(np.frombuffer(buf, dtype="<f4", count=1, offset=7)[0])
+    off, grids = 11, []
+    for _ in range(n_grids):
+        if off + 4 > len(buf):
+            raise ValueError("Residual file truncated: no record count.")
+        (m,) = struct.unpack_from("<I", buf, off); off += 4
+        if off + 5 * m > len(buf):
+            raise ValueError("Residual file truncated: incomplete leaf entry.")
+        ids, classes, recs = np.empty(m, np.int64), np.empty(m, np.uint8), []
+        for i in range(m):
+            if off + 5 > len(buf):
+                raise ValueError("Residual file truncated: incomplete leaf entry.")
+            ri, cls = struct.unpack_from("<IB", buf, off); off += 5
+            if i and ri <= ids[i - 1]:
+                raise ValueError("residual file: record indices are not ascending")
+            size = residual_record_bytes(cls)
+            if off + size > len(buf):
+                raise ValueError("Residual file truncated: incomplete leaf entry.")
+            ids[i], classes[i] = ri, cls
+            recs.append(bytes(buf[off:off + size])); off += size
+        grids.append((ids, classes, recs))
+    if off != len(buf):
+        raise ValueError("Residual file holds bytes past its last grid.")
+    return tol, grids
+
+
+def save_residual_v2(path, tol: float, grids) -> None:
+    with open(path, "wb") as f:
+        f.write(dumps_residual_v2(tol, grids))
+
+
+def load_residual_v2(path):
+    with open(path, "rb") as f:
+        return loads_residual_v2(f.read())
