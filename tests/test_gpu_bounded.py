@@ -278,6 +278,7 @@ def test_file_pair_refuses_a_sidecar_that_does_not_fit(codec, leaves, bounded, t
     tol, err, idx, ids, raw, out = bounded
     grids = grids_of(leaves)
     lossy, res, bad = tmp_path / "b.vqvdb", tmp_path / "b.vqres", tmp_path / "bad.vqres"
+    plain = codec.decode(idx)
     codec.compress_file_bounded(lossy, res, grids, tol, batch_leaves=32)
     rtol, rg = vqvdbfile.load_residual(res)
     assert len(rg[1][0]) >= 2
@@ -308,6 +309,11 @@ def test_file_pair_refuses_a_sidecar_that_does_not_fit(codec, leaves, bounded, t
         codec.decompress_file_bounded(lossy, tmp_path / "absent.vqres")
     # the handle still works
     assert same(np.concatenate([g[3] for g in codec.decompress_file_bounded(lossy, res, batch_leaves=32)[0]]), out)
+    # ... and a refused sidecar leaves no mode behind: the plain calls on the same handle
+    assert same(np.concatenate([g[3] for g in codec.decompress_file(lossy, batch_leaves=32)[0]]), plain) and same(codec.decode(idx), plain)
+    assert np.array_equal(codec.encode(leaves), idx) and same(codec.decode(codec.encode(leaves)), plain)
+    keep = np.setdiff1d(np.arange(N), ids)
+    assert same(plain[keep], out[keep]) and not same(plain, out)
 
 
 def test_file_pair_on_a_grid_whose_single_batch_is_cut_into_pieces(codec, leaves, bounded, tmp_path):

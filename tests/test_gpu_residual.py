@@ -318,6 +318,7 @@ def test_file_pair_refuses_a_sidecar_that_does_not_fit(codec, leaves, resid, tmp
     tol, err, idx, cls, payload, out = resid
     grids = grids_of(leaves)
     lossy, res, bad = tmp_path / "b.vqvdb", tmp_path / "b.vqres", tmp_path / "bad.vqres"
+    plain = codec.decode(idx)
     codec.compress_file_residual(lossy, res, grids, tol, batch_leaves=32)
     rtol, rg = vqvdbfile.load_residual_v2(res)
     assert len(rg[0][0]) >= 2 and len(rg[1][0]) >= 2
@@ -356,3 +357,32 @@ def test_file_pair_refuses_a_sidecar_that_does_not_fit(codec, leaves, resid, tmp
     lib, h = codec._lib, codec._h
     assert lib.vqhip_compress_file_residual(h, b"a", None, None, 1, 0, 0.5, None, None, None) == -1 and "null path" in lib.vqhip_last_error(h).decode()
     assert same(cat(codec.decompress_file_residual(lossy, res, batch_leaves=32)[0]), out)       # the handle still works
+    # ... and a refused sidecar leaves no mode behind: the plain calls on the same handle apply no records
+    assert same(cat(codec.decompress_file(lossy, batch_leaves=32)[0]), plain) and same(codec.decode(idx), plain)
+    assert np.array_equal(codec.encode(leaves), idx) and same(codec.decode(codec.encode(leaves)), plain)
+    assert same(plain[cls == trr.KEPT], out[cls == trr.KEPT]) and not same(plain, out)
+
+
+def test_file_pairs_on_a_batch_cut_into_pieces_of_64_64_and_8(request, codec, pack, leaves, resid, tmp_path, monkeypatch):
+    """One grid of all 136 leaves in one batch, through a handle created with VQHIP_HOST_SPLIT=4,32 (32 is the smallest piece size
+    the variable accepts): the host pipeline cuts the call into pieces of 64, 64 and 8 leaves, so the consumer and the decode stage
+    see offsets inside the batch and both I/O slots.  The v2 pair and the v1 pair write the default handle's bytes and return the
+    host pairs' leaves."""
+    tol, err, idx, cls, payload, out = resid
+    grids = [("density", np.arange(N * 3, dtype=np.int32).reshape(N, 3) * 8, leaves, None)]
+    monkeypatch.setenv("VQHIP_HOST_SPLIT", "4,32")
+    split = HipCodec(pack)
+    monkeypatch.delenv("VQHIP_HOST_SPLIT")
+    try:
+        split.set_small_batch_tiles(request.node.callspec.params["codec"])
+        bidx, ids, raw = codec.compress_bounded(leaves, tol)
+        for name, want in (("residual", out), ("bounded", codec.decompress_bounded(bidx, ids, raw))):
+            files = [tmp_path / f"{who}_{name}{ext}" for who in ("whole", "split") for ext in (".vqvdb", ".vqres")]
+            getattr(codec, "compress_file_" + name)(files[0], files[1], grids, tol, batch_leaves=0)
+            getattr(split, "compress_file_" + name)(files[2], files[3], grids, tol, batch_leaves=0)
+            assert files[2].read_bytes() == files[0].read_bytes() and files[3].read_bytes() == files[1].read_bytes(), name
+            assert len(files[1].read_bytes()) > 15, name                                       # the sidecar holds entries
+            got, st = getattr(split, "decompress_file_" + name)(files[2], files[3], batch_leaves=0)
+            assert st["leaves"] == N and same(cat(got), want), name
+    finally:
+        split.close()

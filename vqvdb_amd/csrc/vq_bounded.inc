@@ -2,7 +2,7 @@
 // _compress_bounded, _decompress_bounded; include/vqvdb_hip_bounded.h, DESIGN.md §16).  Part of vq_runtime.hip's translation
 // unit, after vq_vec3_bounded.inc: it drives encode_chunk and decode_chunk unchanged, measures the chunk with leaf_err_k and
 // selects with the Vec3 handle's compaction kernels.  The file pair lives beside vqhip_compress_file / _decompress_file in
-// vq_runtime.hip, whose pipeline calls bd_pipe_chunk below.
+// vq_file.inc, which hangs bd_stage below behind every chunk of the host pipeline.
 
 #include "vq_bounded.h"
 
@@ -89,12 +89,19 @@ int bd_ensure_pipe(vqhip_codec* c, int64_t m)
     return VQHIP_OK;
 }
 
-// run_pipeline's encode step of a bounded file compress: the slot's chunk is encoded; decode it and measure it
-int bd_pipe_chunk(vqhip_codec* c, const float* d_leaves, const uint8_t* d_idx, int64_t m, int slot, hipStream_t s)
+// a bounded file compress, behind the encode of every chunk: decode it and measure it on the compute stream; its leaf errors follow
+// its indices to c->bd_pin_err[slot], where the pipeline's consumer reads them
+PipeStage bd_stage(vqhip_codec* c)
 {
-    if (int rc = bd_grow(c, c->bd_recon, c->bd_recon_leaves, m * 512, "the reconstruction chunk")) return rc;
-    if (int rc = decode_chunk(c, d_idx, m, c->bd_recon, s)) return rc;
-    return bd_leaf_err(c, d_leaves, c->bd_recon, m, c->bd_err[slot], s);
+    return {[c](int64_t step) { return bd_ensure_pipe(c, step); },
+            [c](int64_t, int64_t m, int slot, hipStream_t s) {
+                if (int rc = bd_grow(c, c->bd_recon, c->bd_recon_leaves, m * 512, "the reconstruction chunk")) return rc;
+                if (int rc = decode_chunk(c, c->dev_idx[slot], m, c->bd_recon, s)) return rc;
+                return bd_leaf_err(c, c->dev_leaves[slot], c->bd_recon, m, c->bd_err[slot], s);
+            },
+            [c](int64_t m, int slot, hipStream_t s) {
+                return hipMemcpyAsync(c->bd_pin_err[slot], c->bd_err[slot], (size_t)m * VQHIP_ERR_FLOATS * sizeof(float), hipMemcpyDeviceToHost, s);
+            }};
 }
 
 int bd_prepare(vqhip_codec* c)

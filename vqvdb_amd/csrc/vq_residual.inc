@@ -1,8 +1,8 @@
 // vq_residual.inc — runtime of the scalar handle's quantised residuals (vqhip_residual_encode_device, _apply_device,
 // _compress_residual, _decompress_residual and the file pair; include/vqvdb_hip_residual.h, DESIGN.md §17).  Part of
 // vq_runtime.hip's translation unit, after vq_bounded.inc: the round trip and its leaf errors are that file's, unchanged; the
-// four kernels of vq_residual.h follow them.  The file pair runs compress_file_impl / decompress_file_impl of vq_runtime.hip,
-// whose pipeline calls rs_pipe_chunk and the handle's rs_decode_hook below.
+// four kernels of vq_residual.h follow them.  The file pair runs compress_file_impl / decompress_file_impl of vq_file.inc,
+// which hang rs_encode_stage / rs_decode_stage below behind every chunk of the host pipeline.
 
 #include "../../include/vqvdb_hip_residual.h"
 #include "vq_residual.h"
@@ -89,37 +89,44 @@ int64_t* rs_pin_off(vqhip_codec* c, int slot) { return reinterpret_cast<int64_t*
 unsigned char* rs_pin_payload(vqhip_codec* c, int slot) { return c->rs_pin[slot] + (size_t)(c->rs_pin_leaves + 2) * 8; }
 unsigned char* rs_pin_class(vqhip_codec* c, int slot) { return rs_pin_payload(c, slot) + (size_t)c->rs_pin_leaves * 2048; }
 
-// run_pipeline's encode step of a residual file compress, behind bd_pipe_chunk: the slot's chunk is measured; class, place, pack
-int rs_pipe_chunk(vqhip_codec* c, const float* d_leaves, int64_t m, int slot, hipStream_t s)
+// a residual file compress: the bounded stage, then the measured chunk is classed, placed and packed into the slot's payload
+// buffer; its total and classes travel to the pinned block behind the leaf errors, and the consumer fetches the payload
+PipeStage rs_encode_stage(vqhip_codec* c, float tol)
 {
-    return rs_encode(c, d_leaves, c->bd_recon, c->bd_err[slot], m, c->rs_tol, c->rs_class[slot], c->rs_off[slot], c->rs_payload[slot], m * 2048, s);
-}
-
-// ... and its classes and total on their way to pinned memory, behind the leaf errors on stream s
-hipError_t rs_pipe_copy_out(vqhip_codec* c, int64_t m, int slot, hipStream_t s)
-{
-    hipError_t e = hipMemcpyAsync(c->rs_pin[slot], c->rs_off[slot] + m, sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(rs_pin_class(c, slot), c->rs_class[slot], (size_t)m, hipMemcpyDeviceToHost, s);
-    return e;
+    const PipeStage bd = bd_stage(c);
+    return {[=](int64_t step) {
+                const int rc = bd.ensure(step);
+                return rc ? rc : rs_ensure(c, step, true);
+            },
+            [=](int64_t o, int64_t m, int slot, hipStream_t s) {
+                const int rc = bd.device(o, m, slot, s);
+                return rc ? rc : rs_encode(c, c->dev_leaves[slot], c->bd_recon, c->bd_err[slot], m, tol, c->rs_class[slot], c->rs_off[slot],
+                                           c->rs_payload[slot], m * 2048, s);
+            },
+            [=](int64_t m, int slot, hipStream_t s) {
+                hipError_t e = bd.copy_out(m, slot, s);
+                if (e == hipSuccess) e = hipMemcpyAsync(c->rs_pin[slot], c->rs_off[slot] + m, sizeof(int64_t), hipMemcpyDeviceToHost, s);
+                if (e == hipSuccess) e = hipMemcpyAsync(rs_pin_class(c, slot), c->rs_class[slot], (size_t)m, hipMemcpyDeviceToHost, s);
+                return e;
+            }};
 }
 
 // the consumer of a residual file compress: the chunk's payload, now that its total is known.  The slot's device buffer is
-// not written again before the consumer returns, and stream c->rs_cur_stream is idle at this point.
-int rs_fetch_payload(vqhip_codec* c, int64_t m, const unsigned char** payload, int64_t* total)
+// not written again before the consumer returns, and the chunk's idle stream carries the copy.
+int rs_fetch_payload(vqhip_codec* c, const PipeChunk& ch, const unsigned char** payload, int64_t* total)
 {
-    const int slot = c->rs_cur_slot;
-    std::memcpy(total, c->rs_pin[slot], sizeof(int64_t));
-    if (*total < 0 || *total > m * 2048) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: payload size out of range");
-    *payload = rs_pin_payload(c, slot);
+    std::memcpy(total, c->rs_pin[ch.slot], sizeof(int64_t));
+    if (*total < 0 || *total > ch.m * 2048) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: payload size out of range");
+    *payload = rs_pin_payload(c, ch.slot);
     if (*total == 0) return VQHIP_OK;
-    HIPCHK(c, hipMemcpyAsync(rs_pin_payload(c, slot), c->rs_payload[slot], (size_t)*total, hipMemcpyDeviceToHost, c->rs_cur_stream));
-    HIPCHK(c, hipStreamSynchronize(c->rs_cur_stream));
+    HIPCHK(c, hipMemcpyAsync(rs_pin_payload(c, ch.slot), c->rs_payload[ch.slot], (size_t)*total, hipMemcpyDeviceToHost, ch.idle));
+    HIPCHK(c, hipStreamSynchronize(ch.idle));
     return VQHIP_OK;
 }
 
 // a residual file decompress: the slot's pinned block holds the chunk's classes and, in leaf order, its records; place them,
 // upload all three and apply them to the decoded chunk on stream s.  The block is not written again before that work is done.
-int rs_upload_apply(vqhip_codec* c, float* d_leaves, int64_t m, int slot, hipStream_t s)
+int rs_upload_apply(vqhip_codec* c, int64_t m, float tol, int slot, hipStream_t s)
 {
     const unsigned char* cls = rs_pin_class(c, slot);
     int64_t* off = rs_pin_off(c, slot);
@@ -129,7 +136,71 @@ int rs_upload_apply(vqhip_codec* c, float* d_leaves, int64_t m, int slot, hipStr
     HIPCHK(c, hipMemcpyAsync(c->rs_class[slot], rs_pin_class(c, slot), (size_t)m, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->rs_off[slot], rs_pin_off(c, slot), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
     if (total > 0) HIPCHK(c, hipMemcpyAsync(c->rs_payload[slot], rs_pin_payload(c, slot), (size_t)total, hipMemcpyHostToDevice, s));
-    return rs_apply(c, d_leaves, m, c->rs_tol, c->rs_class[slot], c->rs_off[slot], c->rs_payload[slot], s);
+    return rs_apply(c, c->dev_leaves[slot], m, tol, c->rs_class[slot], c->rs_off[slot], c->rs_payload[slot], s);
+}
+
+// Forward reader of one grid's entries in a .vqres sidecar: {u32 index | v2: u8 class | record}, indices ascending within the
+// grid of n leaves (v1, vqvdb_hip_bounded.h: every record a raw leaf; v2: vqvdb_hip_residual.h).  The file pair's decompress
+// walks it in step with the chunks: an entry whose header is read but whose leaf lies in a later chunk stays pending.
+struct ResidualWalk {
+    vqhip_codec* c;
+    FILE* fr;
+    bool v2;
+    const std::string& name;
+    int64_t n;
+    int64_t left = 0, pending = -1, prev = -1;   // entries still to take, the index read ahead (-1: none), the last one taken
+    int cls = VQHIP_RES_RAW;                     // the class read with `pending`
+
+    // every entry of chunk [o, o + m), in order: dst(leaf within the chunk, class) is where its record goes
+    template <typename Dst>
+    int read_chunk(int64_t o, int64_t m, Dst&& dst)
+    {
+        while (left > 0) {
+            if (pending < 0) {
+                unsigned char eh[5];
+                const size_t hb = v2 ? 5 : 4;
+                uint32_t ri = 0;
+                if (std::fread(eh, 1, hb, fr) != hb) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
+                std::memcpy(&ri, eh, 4);
+                if ((int64_t)ri >= n)
+                    return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' of " + std::to_string(n) + " leaves");
+                if ((int64_t)ri <= prev)
+                    return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' is not ascending");
+                if (v2 && eh[4] > 16 && eh[4] != VQHIP_RES_RAW)
+                    return fail(c, VQHIP_ERR_INVALID, "residual file: class " + std::to_string((int)eh[4]) + " of record " + std::to_string(ri) + " in grid '" + name +
+                                                          "' is not 0..16 or 255");
+                pending = ri;
+                if (v2) cls = eh[4];
+            }
+            if (pending >= o + m) break;   // a later chunk's leaf (earlier ones went with their chunk: pending >= o)
+            const size_t sz = (size_t)rs_record_size(cls);
+            void* to = dst(pending - o, cls);   // also for a class of no bytes
+            if (sz && std::fread(to, 1, sz, fr) != sz) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
+            prev = pending, pending = -1, --left;
+        }
+        return VQHIP_OK;
+    }
+};
+
+// a residual file decompress (.vqres v2), behind the decode of the slot's chunk on stream s: the chunk's records are read forward
+// into the slot's pinned block, uploaded and applied before the chunk leaves the GPU.  *walk outlives the pipeline run.
+PipeStage rs_decode_stage(vqhip_codec* c, float tol, ResidualWalk* walk)
+{
+    return {[c](int64_t step) { return rs_ensure(c, step, true); },
+            [c, tol, walk](int64_t o, int64_t m, int slot, hipStream_t s) {
+                unsigned char* cls = rs_pin_class(c, slot);
+                unsigned char* pay = rs_pin_payload(c, slot);
+                bool any = false;
+                const int rc = walk->read_chunk(o, m, [&](int64_t l, int k) {
+                    if (!any) std::memset(cls, VQHIP_RES_KEPT, (size_t)m), any = true;
+                    cls[l] = (unsigned char)k;
+                    unsigned char* at = pay;
+                    pay += rs_record_size(k);
+                    return at;
+                });
+                return rc || !any ? rc : rs_upload_apply(c, m, tol, slot, s);
+            },
+            nullptr};
 }
 
 }  // namespace
@@ -238,22 +309,6 @@ int vqhip_decompress_residual(vqhip_codec* c, const uint8_t* indices, int64_t n,
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return VQHIP_OK;
-}
-
-int vqhip_compress_file_residual(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
-                                 int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats, vqhip_residual_stats* rstats)
-{
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !residual_path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file_residual: null path, residual path or grid list");
-    return compress_file_impl(c, path, residual_path, grids, n_grids, batch_leaves, tol, stats, bstats, 2, rstats);
-}
-
-int vqhip_decompress_file_residual(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
-                                   vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats)
-{
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !residual_path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file_residual: null path, residual path or leaf allocator");
-    return decompress_file_impl(c, path, residual_path, batch_leaves, grid_begin, leaf_alloc, user, stats, 2);
 }
 
 }  // extern "C"

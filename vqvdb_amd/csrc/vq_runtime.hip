@@ -285,8 +285,6 @@ struct vqhip_codec {
     int64_t bd_ids_n = 0;
     int64_t* bd_scan = nullptr;     // block counts / offsets of the selection
     int64_t bd_scan_n = 0;
-    bool bd_pipe = false;           // run_pipeline: every encoded chunk is also decoded and measured (vqhip_compress_file_bounded)
-    const float* bd_pin_cur = nullptr;   // ... the leaf errors of the chunk being consumed
     // quantised residuals (vq_residual.inc): lazy, sized to the largest chunk seen, freed in vqhip_destroy; one set per I/O slot
     uint8_t* rs_class[2] = {nullptr, nullptr};
     int64_t* rs_off[2] = {nullptr, nullptr};
@@ -294,12 +292,6 @@ struct vqhip_codec {
     int64_t rs_leaves = 0;
     unsigned char* rs_pin[2] = {nullptr, nullptr};   // the file pair's pinned block: total, offsets, payload, classes
     int64_t rs_pin_leaves = 0;
-    bool rs_pipe = false;           // run_pipeline: every measured chunk is also classed, placed and packed (vqhip_compress_file_residual)
-    float rs_tol = 0.0f;            // ... at this tolerance
-    int rs_cur_slot = 0;            // ... the slot of the chunk being consumed and an idle stream for the consumer's payload fetch
-    hipStream_t rs_cur_stream = nullptr;
-    // run_pipeline: called behind every decoded chunk (offset, leaves, slot, the chunk on the device, its stream); vqhip_decompress_file_residual
-    std::function<int(int64_t, int64_t, int, float*, hipStream_t)> rs_decode_hook;
 };
 
 namespace {
@@ -1674,27 +1666,24 @@ int ensure_tables(vqhip_codec* c)
 // encode: in = leaves (2048 B/leaf), out = indices (64 B/leaf); decode: the reverse.
 //   produce(o, m, stage): returns the host address of chunk [o, o+m)'s input; `stage` is this slot's pinned
 //                         buffer (nullptr unless want_stage) which produce may fill and return.
-//   consume(o, m, result): result = pinned buffer holding the chunk's output.
+//   consume(chunk): the chunk's output lies in pinned memory at chunk.result.
+//   stage (optional): more work behind every chunk, built where its buffers live (vq_bounded.inc, vq_residual.inc).
+struct PipeChunk {
+    int64_t o, m;         // leaves [o, o + m) of the call
+    int slot;             // the I/O slot they went through: its buffers are not written again before consume() returns
+    const void* result;
+    hipStream_t idle;     // a stream with nothing queued while consume() runs, for a consumer that fetches more of the slot
+};
 using ProduceFn = std::function<const void*(int64_t, int64_t, void*)>;
-using ConsumeFn = std::function<int(int64_t, int64_t, const void*)>;
+using ConsumeFn = std::function<int(const PipeChunk&)>;
+struct PipeStage {   // empty members are skipped
+    std::function<int(int64_t step)> ensure;                                    // buffers for chunks of <= step leaves, both slots
+    std::function<int(int64_t o, int64_t m, int slot, hipStream_t s)> device;   // on the compute stream, behind the chunk's encode / decode
+    std::function<hipError_t(int64_t m, int slot, hipStream_t s)> copy_out;     // on the output stream, behind the result's D2H
+};
 
-// vq_bounded.inc: with c->bd_pipe set, an encoding pipeline also decodes every chunk and measures its leaves; consume()
-// then finds the chunk's leaf errors at c->bd_pin_cur
-int bd_ensure_pipe(vqhip_codec* c, int64_t m);
-int bd_pipe_chunk(vqhip_codec* c, const float* d_leaves, const uint8_t* d_idx, int64_t m, int slot, hipStream_t s);
-// vq_residual.inc: with c->rs_pipe set as well, the measured chunk is classed, placed and packed into the slot's payload buffer;
-// its classes and total travel behind the leaf errors, and consume() fetches the payload with rs_fetch_payload
-int rs_ensure(vqhip_codec* c, int64_t m, bool pinned);
-int rs_pipe_chunk(vqhip_codec* c, const float* d_leaves, int64_t m, int slot, hipStream_t s);
-hipError_t rs_pipe_copy_out(vqhip_codec* c, int64_t m, int slot, hipStream_t s);
-int rs_fetch_payload(vqhip_codec* c, int64_t m, const unsigned char** payload, int64_t* total);
-// ... and a decoding pipeline calls c->rs_decode_hook behind every decoded chunk; the hook stages the chunk's classes and records
-// in the slot's pinned block and hands them to rs_upload_apply
-unsigned char* rs_pin_class(vqhip_codec* c, int slot);
-unsigned char* rs_pin_payload(vqhip_codec* c, int slot);
-int rs_upload_apply(vqhip_codec* c, float* d_leaves, int64_t m, int slot, hipStream_t s);
-
-int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool want_stage, const ProduceFn& produce, const ConsumeFn& consume)
+int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool want_stage, const ProduceFn& produce, const ConsumeFn& consume,
+                 const PipeStage* stage = nullptr)
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->chunk_fitted) fit_chunk_to_free_memory(c), c->chunk_fitted = true;
@@ -1711,16 +1700,26 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
     if (rc) return rc;
     const size_t in_b = is_encode ? 2048 : 64, out_b = is_encode ? 64 : 2048;
     if (want_stage && (rc = ensure_stage(c, (size_t)step * in_b))) return rc;
-    const bool bounded = is_encode && c->bd_pipe;
-    if (bounded && (rc = bd_ensure_pipe(c, step))) return rc;
-    const bool resid = bounded && c->rs_pipe;
-    if ((resid || (!is_encode && c->rs_decode_hook)) && (rc = rs_ensure(c, step, true))) return rc;
+    if (stage && stage->ensure && (rc = stage->ensure(step))) return rc;
+    // what every chunk gets, in either arrangement below: its kernels on the compute stream ...
+    auto chunk_work = [&](int64_t o, int64_t m, int slot) -> int {
+        int r = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream)
+                          : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream);
+        if (!r && stage && stage->device) r = stage->device(o, m, slot, c->stream);
+        return r;
+    };
+    // ... and its results on their way to pinned memory on stream s, the stage's behind the main one
+    auto copy_out = [&](int64_t m, int slot, hipStream_t s) -> hipError_t {
+        const void* d_out = is_encode ? (const void*)c->dev_idx[slot] : (const void*)c->dev_leaves[slot];
+        hipError_t e = hipMemcpyAsync(c->pin_out[slot], d_out, (size_t)m * out_b, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && stage && stage->copy_out) e = stage->copy_out(m, slot, s);
+        return e;
+    };
     if (n <= step) {
         // One chunk: there is nothing to overlap — H2D, kernels and D2H go down the compute stream in order and the call waits once.
         // (The three-stream form below costs such a call three cross-stream event hand-overs and as many extra API calls: the SOP's
         // default batch of 64 leaves is a 0.14-0.20 ms pass, so they showed: 0.26 / 0.21 ms per call through the adapter.)
         void* d_in = is_encode ? (void*)c->dev_leaves[0] : (void*)c->dev_idx[0];
-        void* d_out = is_encode ? (void*)c->dev_idx[0] : (void*)c->dev_leaves[0];
         const void* src = produce(0, n, want_stage ? c->pin_in[0] : nullptr);
         if (!src) return c->err.empty() ? fail(c, VQHIP_ERR_INVALID, "input source failed") : VQHIP_ERR_INVALID;
         auto sync_fail = [&](int code) {   // leave no copy in flight that references caller or slot memory
@@ -1729,20 +1728,12 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         };
         hipError_t e = hipMemcpyAsync(d_in, src, (size_t)n * in_b, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) return sync_fail(fail(c, VQHIP_ERR_DEVICE, std::string("hipMemcpyAsync H2D: ") + hipGetErrorString(e)));
-        rc = is_encode ? encode_chunk(c, c->dev_leaves[0], n, c->dev_idx[0], c->stream) : decode_chunk(c, c->dev_idx[0], n, c->dev_leaves[0], c->stream);
-        if (!rc && bounded) rc = bd_pipe_chunk(c, c->dev_leaves[0], c->dev_idx[0], n, 0, c->stream);
-        if (!rc && resid) rc = rs_pipe_chunk(c, c->dev_leaves[0], n, 0, c->stream);
-        if (!rc && !is_encode && c->rs_decode_hook) rc = c->rs_decode_hook(0, n, 0, c->dev_leaves[0], c->stream);
-        if (rc) return sync_fail(rc);
-        e = hipMemcpyAsync(c->pin_out[0], d_out, (size_t)n * out_b, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && bounded) e = hipMemcpyAsync(c->bd_pin_err[0], c->bd_err[0], (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess && resid) e = rs_pipe_copy_out(c, n, 0, c->stream);
+        if ((rc = chunk_work(0, n, 0))) return sync_fail(rc);
+        e = copy_out(n, 0, c->stream);
         if (e != hipSuccess) return sync_fail(fail(c, VQHIP_ERR_DEVICE, std::string("hipMemcpyAsync D2H: ") + hipGetErrorString(e)));
         e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(c, VQHIP_ERR_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
-        c->bd_pin_cur = c->bd_pin_err[0];
-        c->rs_cur_slot = 0, c->rs_cur_stream = c->stream;
-        return consume(0, n, c->pin_out[0]);
+        return consume({0, n, 0, c->pin_out[0], c->stream});
     }
     int64_t prev_off = -1, prev_m = 0;
     int prev_slot = 0, i = 0;
@@ -1751,9 +1742,7 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         HIPCHK(c, hipEventSynchronize(c->ev_out[prev_slot]));
         const int64_t o = prev_off;
         prev_off = -1;
-        c->bd_pin_cur = c->bd_pin_err[prev_slot];
-        c->rs_cur_slot = prev_slot, c->rs_cur_stream = c->s_out;   // s_out is idle here: the next chunk's copies are queued after this drain
-        return consume(o, prev_m, c->pin_out[prev_slot]);
+        return consume({o, prev_m, prev_slot, c->pin_out[prev_slot], c->s_out});   // s_out is idle here: the next chunk's copies are queued after this drain
     };
     auto abort_run = [&](int code) {  // leave no work in flight that still references caller memory
         hipStreamSynchronize(c->s_in);
@@ -1774,7 +1763,6 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         const int64_t m = std::min(step, n - o);
         const int slot = i & 1;
         void* d_in = is_encode ? (void*)c->dev_leaves[slot] : (void*)c->dev_idx[slot];
-        void* d_out = is_encode ? (void*)c->dev_idx[slot] : (void*)c->dev_leaves[slot];
         if (i >= 2) PIPECHK(hipStreamWaitEvent(c->s_in, c->ev_done[slot], 0));  // slot's previous input consumed
         if (want_stage && i >= 2) PIPECHK(hipEventSynchronize(c->ev_in[slot]));  // the H2D that last read this pinned buffer is done
         const void* src = produce(o, m, want_stage ? c->pin_in[slot] : nullptr);
@@ -1783,18 +1771,11 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
         PIPECHK(hipEventRecord(c->ev_in[slot], c->s_in));
         PIPECHK(hipStreamWaitEvent(c->stream, c->ev_in[slot], 0));
         if (i >= 2) PIPECHK(hipStreamWaitEvent(c->stream, c->ev_out[slot], 0));  // slot's previous output drained to pinned
-        rc = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream)
-                       : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream);
-        if (!rc && bounded) rc = bd_pipe_chunk(c, c->dev_leaves[slot], c->dev_idx[slot], m, slot, c->stream);
-        if (!rc && resid) rc = rs_pipe_chunk(c, c->dev_leaves[slot], m, slot, c->stream);
-        if (!rc && !is_encode && c->rs_decode_hook) rc = c->rs_decode_hook(o, m, slot, c->dev_leaves[slot], c->stream);
-        if (rc) return abort_run(rc);
+        if ((rc = chunk_work(o, m, slot))) return abort_run(rc);
         PIPECHK(hipEventRecord(c->ev_done[slot], c->stream));
         if ((rc = drain())) return abort_run(rc);  // chunk i-1 -> caller, overlapped with chunk i on the GPU
         PIPECHK(hipStreamWaitEvent(c->s_out, c->ev_done[slot], 0));
-        PIPECHK(hipMemcpyAsync(c->pin_out[slot], d_out, (size_t)m * out_b, hipMemcpyDeviceToHost, c->s_out));
-        if (bounded) PIPECHK(hipMemcpyAsync(c->bd_pin_err[slot], c->bd_err[slot], (size_t)m * 2 * sizeof(float), hipMemcpyDeviceToHost, c->s_out));
-        if (resid) PIPECHK(rs_pipe_copy_out(c, m, slot, c->s_out));
+        PIPECHK(copy_out(m, slot, c->s_out));
         PIPECHK(hipEventRecord(c->ev_out[slot], c->s_out));
         prev_off = o, prev_m = m, prev_slot = slot;
     }
@@ -1835,40 +1816,12 @@ int run_host_pipeline(vqhip_codec* c, bool is_encode, const void* in, void* out,
             else host_parallel_copy(stage, src, (size_t)m * in_b);
             return stage;
         },
-        [=](int64_t o, int64_t m, const void* res) -> int {
-            if (out_ptrs) scatter_leaves(out_ptrs + o, static_cast<const float*>(res), m);
-            else host_parallel_copy(static_cast<char*>(out) + (size_t)o * out_b, res, (size_t)m * out_b);
+        [=](const PipeChunk& ch) -> int {
+            if (out_ptrs) scatter_leaves(out_ptrs + ch.o, static_cast<const float*>(ch.result), ch.m);
+            else host_parallel_copy(static_cast<char*>(out) + (size_t)ch.o * out_b, ch.result, (size_t)ch.m * out_b);
             return VQHIP_OK;
         });
 }
-
-// ---------------- .vqvdb v3 container (reference src/Utils/VQVDB_Reader.{hpp,cpp}) ----------------
-// file : "VQVDB" | u8 version=3 | u8 numGrids | u32 numEmbeddings | u8 latentDimCount
-// grid : u32 nameLength | name | f32 transform[16] | u16 latentShape[latentDimCount] | u32 totalBlocks
-//        totalBlocks x { i32 origin[3] | u8 indices[64] }   (76 B per leaf)
-constexpr size_t REC_BYTES = 76;
-
-double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-struct FileCloser {
-    FILE* f;
-    ~FileCloser()
-    {
-        if (f) std::fclose(f);
-    }
-};
-
-// One decoded-side batch travelling from the reader thread to the pipeline: indices de-framed from the records,
-// origins, and the leaf addresses the caller's allocator returned for them.
-struct StreamBatch {
-    std::vector<uint8_t> idx;
-    std::vector<int32_t> origins;
-    std::vector<float*> ptrs;
-    std::vector<unsigned char> raw;
-};
 
 }  // namespace
 
@@ -2114,433 +2067,6 @@ int vqhip_decode_leaves(vqhip_codec* c, const uint8_t* indices, int64_t n, float
     if (!c) return VQHIP_ERR_INVALID;
     if (!leaf_ptrs || !indices || n < 1) return fail(c, VQHIP_ERR_INVALID, "decode_leaves: null pointer or n_leaves < 1");
     return run_host_pipeline(c, false, indices, nullptr, n, nullptr, leaf_ptrs);
-}
-
-// ---- .vqvdb stream entry points: file read || GPU decode || leaf insert ----
-// Replaces the body of VQVAECodec::decompress (VQVAECodec.cpp:137-208): per grid, a reader thread reads and de-frames
-// batch k+1..k+2 and asks the caller's allocator for their leaf buffers while the GPU decodes batch k and the calling
-// thread scatters batch k-1 straight from pinned memory into those buffers.
-//
-// residual_path (vqhip_decompress_file_bounded, NULL otherwise): a .vqres sidecar (vqvdb_hip_bounded.h) read in step with the
-// batches; after a batch's scatter the leaves it names are overwritten with its floats.  res_version 2
-// (vqhip_decompress_file_residual): a .vqres v2 sidecar (vqvdb_hip_residual.h); the records of a decoded batch are read forward,
-// uploaded and applied on the GPU before the batch leaves it.
-static int decompress_file_impl(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
-                                vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats, int res_version = 1)
-{
-    FILE* f = std::fopen(path, "rb");
-    if (!f) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open input file: ") + path);
-    FileCloser closer{f};
-    const double t_start = now_s();
-    vqhip_stream_stats st;
-    std::memset(&st, 0, sizeof st);
-    unsigned char h[12];
-    if (std::fread(h, 1, 12, f) != 12) return fail(c, VQHIP_ERR_INVALID, "Failed to read file header.");
-    if (std::memcmp(h, "VQVDB", 5) != 0) return fail(c, VQHIP_ERR_INVALID, "Invalid file magic; not a .vqvdb file.");
-    if (h[5] != 3) return fail(c, VQHIP_ERR_INVALID, "Unsupported .vqvdb version " + std::to_string((int)h[5]) + " (expected 3).");
-    const int n_grids = h[6], dim_count = h[11];
-    uint32_t num_emb;
-    std::memcpy(&num_emb, h + 7, 4);
-    if (dim_count != 3) return fail(c, VQHIP_ERR_INVALID, "latent rank " + std::to_string(dim_count) + " in file; this codec decodes [4,4,4] latents");
-    FILE* fr = nullptr;
-    if (residual_path) {
-        if (!(fr = std::fopen(residual_path, "rb"))) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open residual file: ") + residual_path);
-    }
-    FileCloser rcloser{fr};
-    if (fr) {
-        unsigned char rh[11];
-        if (std::fread(rh, 1, 11, fr) != 11) return fail(c, VQHIP_ERR_INVALID, "Failed to read residual file header.");
-        if (std::memcmp(rh, "VQRES", 5) != 0) return fail(c, VQHIP_ERR_INVALID, "Invalid residual file magic; not a .vqres file.");
-        if (rh[5] != res_version)
-            return fail(c, VQHIP_ERR_INVALID, "Unsupported .vqres version " + std::to_string((int)rh[5]) + " (expected " + std::to_string(res_version) + ").");
-        std::memcpy(&c->rs_tol, rh + 7, 4);
-        if (rh[6] != n_grids)
-            return fail(c, VQHIP_ERR_INVALID, "residual file holds " + std::to_string((int)rh[6]) + " grids, the .vqvdb file " + std::to_string(n_grids));
-    }
-
-    for (int g = 0; g < n_grids; ++g) {
-        vqhip_grid_info gi;
-        std::memset(&gi, 0, sizeof gi);
-        uint32_t name_len = 0, total = 0;
-        uint16_t shp[3];
-        std::string name;
-        if (std::fread(&name_len, 4, 1, f) != 1 || name_len > (1u << 20)) return fail(c, VQHIP_ERR_INVALID, "Failed to read grid name length.");
-        name.resize(name_len);
-        if (name_len && std::fread(&name[0], 1, name_len, f) != name_len) return fail(c, VQHIP_ERR_INVALID, "Failed to read grid name.");
-        if (std::fread(gi.transform, 4, 16, f) != 16) return fail(c, VQHIP_ERR_INVALID, "Failed to read transform.");
-        if (std::fread(shp, 2, 3, f) != 3) return fail(c, VQHIP_ERR_INVALID, "Failed to read latent shape.");
-        if (std::fread(&total, 4, 1, f) != 1) return fail(c, VQHIP_ERR_INVALID, "File appears truncated, failed to read total block count.");
-        if (shp[0] != 4 || shp[1] != 4 || shp[2] != 4)
-            return fail(c, VQHIP_ERR_INVALID, "grid '" + name + "' has latent shape [" + std::to_string(shp[0]) + "," + std::to_string(shp[1]) + "," +
-                                                  std::to_string(shp[2]) + "]; this codec decodes [4,4,4]");
-        gi.name = name.c_str();
-        gi.grid_index = g;
-        for (int i = 0; i < 3; ++i) gi.latent_shape[i] = shp[i];
-        gi.num_embeddings = num_emb;
-        gi.total_blocks = total;
-        if (grid_begin && grid_begin(user, &gi) != 0) return fail(c, VQHIP_ERR_INVALID, "grid_begin callback failed for grid '" + name + "'");
-        ++st.grids;
-        const int64_t n = total;
-        // sidecar entries of this grid: res_left still to apply, res_next the record index already read (-1: none), res_prev the last applied
-        int64_t res_left = 0, res_next = -1, res_prev = -1;
-        if (fr) {
-            uint32_t n_out = 0;
-            if (std::fread(&n_out, 4, 1, fr) != 1) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: no outlier count for grid '" + name + "'.");
-            if ((int64_t)n_out > n)
-                return fail(c, VQHIP_ERR_INVALID, "residual file: grid '" + name + "' lists " + std::to_string(n_out) + " leaves, the grid has " + std::to_string(n));
-            res_left = n_out;
-        }
-        auto apply_residual = [&](int64_t o, int64_t m, float* const* ptrs) -> int {
-            while (res_left > 0) {
-                if (res_next < 0) {
-                    uint32_t ri = 0;
-                    if (std::fread(&ri, 4, 1, fr) != 1) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
-                    if ((int64_t)ri >= n)
-                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' of " + std::to_string(n) + " leaves");
-                    if ((int64_t)ri <= res_prev)
-                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' is not ascending");
-                    res_next = ri;
-                }
-                if (res_next >= o + m) break;   // a later batch's leaf (earlier ones were applied with their batch: res_next >= o)
-                if (std::fread(ptrs[res_next - o], 4, 512, fr) != 512) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
-                res_prev = res_next, res_next = -1, --res_left;
-            }
-            return VQHIP_OK;
-        };
-        // v2: the same walk behind every decoded chunk, into the slot's pinned block; res_class is the class already read with res_next
-        int res_class = 0;
-        auto stage_residual = [&](int64_t o, int64_t m, int slot, float* d_leaves, hipStream_t s) -> int {
-            unsigned char* cls = rs_pin_class(c, slot);
-            unsigned char* pay = rs_pin_payload(c, slot);
-            bool any = false;
-            while (res_left > 0) {
-                if (res_next < 0) {
-                    unsigned char eh[5];
-                    uint32_t ri = 0;
-                    if (std::fread(eh, 1, 5, fr) != 5) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
-                    std::memcpy(&ri, eh, 4);
-                    if ((int64_t)ri >= n)
-                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' of " + std::to_string(n) + " leaves");
-                    if ((int64_t)ri <= res_prev)
-                        return fail(c, VQHIP_ERR_INVALID, "residual file: record index " + std::to_string(ri) + " in grid '" + name + "' is not ascending");
-                    if (eh[4] > 16 && eh[4] != VQHIP_RES_RAW)
-                        return fail(c, VQHIP_ERR_INVALID, "residual file: class " + std::to_string((int)eh[4]) + " of record " + std::to_string(ri) + " in grid '" + name +
-                                                              "' is not 0..16 or 255");
-                    res_next = ri, res_class = eh[4];
-                }
-                if (res_next >= o + m) break;   // a later chunk's leaf
-                if (!any) std::memset(cls, VQHIP_RES_KEPT, (size_t)m), any = true;
-                const size_t sz = res_class == VQHIP_RES_RAW ? 2048 : 64 * (size_t)res_class;
-                if (sz && std::fread(pay, 1, sz, fr) != sz) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
-                pay += sz;
-                cls[res_next - o] = (unsigned char)res_class;
-                res_prev = res_next, res_next = -1, --res_left;
-            }
-            return any ? rs_upload_apply(c, d_leaves, m, slot, s) : VQHIP_OK;
-        };
-        struct HookGuard {   // the pipeline applies records for as long as this grid's run lasts, whichever way it ends
-            vqhip_codec* c;
-            ~HookGuard() { c->rs_decode_hook = nullptr; }
-        } hook_guard{c};
-        const bool v2 = fr && res_version == 2;
-        if (v2) c->rs_decode_hook = stage_residual;
-        if (n == 0) continue;
-        const int64_t step = std::min(batch_leaves > 0 ? std::min(batch_leaves, c->chunk) : c->chunk, n);
-        const int64_t nb = (n + step - 1) / step;
-
-        constexpr int Q = 3;
-        StreamBatch slot[Q];
-        std::mutex mu;
-        std::condition_variable cv;
-        int64_t produced = 0, consumed = 0;
-        bool failed = false, stop = false;
-        std::string herr;
-        double read_s = 0, alloc_s = 0, wait_s = 0, copy_s = 0;
-        std::thread reader([&] {
-            auto bail = [&](const std::string& m) {
-                std::lock_guard<std::mutex> lk(mu);
-                herr = m;
-                failed = true;
-                cv.notify_all();
-            };
-            for (int64_t k = 0; k < nb; ++k) {
-                {
-                    std::unique_lock<std::mutex> lk(mu);
-                    cv.wait(lk, [&] { return stop || k - consumed < Q; });
-                    if (stop) return;
-                }
-                const int64_t m = std::min(step, n - k * step);
-                StreamBatch& B = slot[k % Q];
-                double t = now_s();
-                B.raw.resize((size_t)m * REC_BYTES);
-                if (std::fread(B.raw.data(), REC_BYTES, (size_t)m, f) != (size_t)m) return bail("File truncated: incomplete block data.");
-                B.idx.resize((size_t)m * 64);
-                B.origins.resize((size_t)m * 3);
-                B.ptrs.assign((size_t)m, nullptr);
-                const unsigned char* p = B.raw.data();
-                for (int64_t l = 0; l < m; ++l, p += REC_BYTES) {
-                    std::memcpy(&B.origins[3 * l], p, 12);
-                    std::memcpy(&B.idx[64 * l], p + 12, 64);
-                }
-                read_s += now_s() - t;
-                t = now_s();
-                const int rc = leaf_alloc(user, g, B.origins.data(), m, B.ptrs.data());
-                alloc_s += now_s() - t;
-                if (rc != 0) return bail("leaf_alloc callback failed (" + std::to_string(rc) + ")");
-                for (int64_t l = 0; l < m; ++l)
-                    if (!B.ptrs[l]) return bail("leaf_alloc callback left a null leaf pointer");
-                std::lock_guard<std::mutex> lk(mu);
-                produced = k + 1;
-                cv.notify_all();
-            }
-        });
-        const int rc = run_pipeline(
-            c, false, n, step, false,
-            [&](int64_t o, int64_t, void*) -> const void* {
-                const int64_t k = o / step;
-                const double t = now_s();
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed || produced > k; });
-                wait_s += now_s() - t;
-                if (produced <= k) {
-                    c->err = herr;
-                    return nullptr;
-                }
-                return slot[k % Q].idx.data() + (o - k * step) * 64;   // run_pipeline may cut a batch into pieces (host_split)
-            },
-            [&](int64_t o, int64_t m, const void* res) -> int {
-                const int64_t k = o / step;
-                float* const* ptrs = slot[k % Q].ptrs.data() + (o - k * step);
-                const double t = now_s();
-                scatter_leaves(ptrs, static_cast<const float*>(res), m);
-                const int rrc = fr && !v2 ? apply_residual(o, m, ptrs) : VQHIP_OK;
-                copy_s += now_s() - t;
-                if (o + m < std::min(n, (k + 1) * step)) return rrc;   // a piece of the batch: its slot is still in use
-                std::lock_guard<std::mutex> lk(mu);
-                consumed = k + 1;
-                cv.notify_all();
-                return rrc;
-            });
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            stop = true;
-            cv.notify_all();
-        }
-        reader.join();
-        if (rc) return rc;
-        st.leaves += n;
-        st.read_s += read_s, st.alloc_s += alloc_s, st.io_wait_s += wait_s, st.copy_s += copy_s;
-    }
-    st.wall_s = now_s() - t_start;
-    if (stats) *stats = st;
-    return VQHIP_OK;
-}
-
-int vqhip_decompress_file(vqhip_codec* c, const char* path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin, vqhip_leaf_alloc_fn leaf_alloc,
-                          void* user, vqhip_stream_stats* stats)
-{
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file: null path or leaf allocator");
-    return decompress_file_impl(c, path, nullptr, batch_leaves, grid_begin, leaf_alloc, user, stats);
-}
-
-int vqhip_decompress_file_bounded(vqhip_codec* c, const char* path, const char* residual_path, int64_t batch_leaves, vqhip_grid_begin_fn grid_begin,
-                                  vqhip_leaf_alloc_fn leaf_alloc, void* user, vqhip_stream_stats* stats)
-{
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !residual_path || !leaf_alloc) return fail(c, VQHIP_ERR_INVALID, "decompress_file_bounded: null path, residual path or leaf allocator");
-    return decompress_file_impl(c, path, residual_path, batch_leaves, grid_begin, leaf_alloc, user, stats);
-}
-
-// Replaces the body of VQVAECodec::compress (VQVAECodec.cpp:78-134): gather the leaf buffers into pinned memory,
-// encode on the GPU, frame {origin, 64 indices} records and append them to the file while the next batch encodes.
-//
-// residual_path (vqhip_compress_file_bounded, NULL otherwise): every chunk is also decoded and measured (c->bd_pipe); the leaves
-// with !(max error <= tol) go raw, from the caller's leaf buffers, into a .vqres sidecar (vqvdb_hip_bounded.h).  The .vqvdb
-// bytes are the same either way.  res_version 2 (vqhip_compress_file_residual): the measured chunk is also classed and packed
-// (c->rs_pipe) and the sidecar holds each selected leaf's record, quantised or raw (.vqres v2, vqvdb_hip_residual.h).
-static int compress_file_impl(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
-                              int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats, int res_version = 1,
-                              vqhip_residual_stats* rstats = nullptr)
-{
-    if (n_grids < 1 || n_grids > 255) return fail(c, VQHIP_ERR_INVALID, "compress_file: a .vqvdb file holds 1..255 grids");
-    for (int g = 0; g < n_grids; ++g) {
-        const vqhip_grid_source& G = grids[g];
-        if (!G.name || G.n_leaves < 0 || G.n_leaves > 0xFFFFFFFFll || (G.n_leaves > 0 && (!G.leaf_ptrs || !G.origins)))
-            return fail(c, VQHIP_ERR_INVALID, "compress_file: grid " + std::to_string(g) + " has no name, no leaves/origins or more than 2^32-1 leaves");
-    }
-    FILE* f = std::fopen(path, "wb");
-    if (!f) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open output file: ") + path);
-    FileCloser closer{f};
-    FILE* fr = nullptr;
-    if (residual_path) {
-        if (!(fr = std::fopen(residual_path, "wb"))) return fail(c, VQHIP_ERR_INVALID, std::string("Cannot open residual file: ") + residual_path);
-    }
-    FileCloser rcloser{fr};
-    struct PipeFlag {   // the pipeline measures its chunks for as long as this call runs, whichever way it ends
-        vqhip_codec* c;
-        ~PipeFlag() { c->bd_pipe = false, c->rs_pipe = false; }
-    } pipe_flag{c};
-    c->bd_pipe = fr != nullptr;
-    const bool v2 = fr && res_version == 2;
-    c->rs_pipe = v2, c->rs_tol = tol;
-    vqhip_residual_stats rst;
-    std::memset(&rst, 0, sizeof rst);
-    std::vector<unsigned char> rrec;   // v2: a chunk's framed entries
-    vqhip_bounded_stats bst;
-    std::memset(&bst, 0, sizeof bst);
-    const double t_start = now_s();
-    vqhip_stream_stats st;
-    std::memset(&st, 0, sizeof st);
-    bool wfail = false;
-    auto put = [&](const void* p, size_t n) {
-        if (n && std::fwrite(p, 1, n, f) != n) wfail = true;
-    };
-    bool rfail = false;
-    auto rput = [&](const void* p, size_t n) {
-        if (std::fwrite(p, 1, n, fr) != n) rfail = true;
-    };
-    if (fr) {
-        unsigned char rh[11];
-        std::memcpy(rh, "VQRES", 5);
-        rh[5] = (unsigned char)res_version;
-        rh[6] = (unsigned char)n_grids;
-        std::memcpy(rh + 7, &tol, 4);
-        rput(rh, 11);
-    }
-    unsigned char h[12];
-    std::memcpy(h, "VQVDB", 5);
-    h[5] = 3;
-    h[6] = (unsigned char)n_grids;
-    const uint32_t num_emb = 256;
-    std::memcpy(h + 7, &num_emb, 4);
-    h[11] = 3;
-    put(h, 12);
-    std::vector<unsigned char> rec;
-    for (int g = 0; g < n_grids; ++g) {
-        const vqhip_grid_source& G = grids[g];
-        static const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-        const uint32_t name_len = (uint32_t)std::strlen(G.name), total = (uint32_t)G.n_leaves;
-        const uint16_t shp[3] = {4, 4, 4};
-        put(&name_len, 4);
-        put(G.name, name_len);
-        put(G.transform ? G.transform : ident, 64);
-        put(shp, 6);
-        put(&total, 4);
-        ++st.grids;
-        if (wfail) return fail(c, VQHIP_ERR_INVALID, "Failed to write to .vqvdb file.");
-        long count_pos = 0;
-        uint32_t grid_out = 0;   // the grid's outlier count: a placeholder now, patched in once the grid is done
-        if (fr) {
-            count_pos = std::ftell(fr);
-            rput(&grid_out, 4);
-            if (rfail || count_pos < 0) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
-        }
-        if (G.n_leaves == 0) continue;
-        double copy_s = 0, write_s = 0;
-        const int rc = run_pipeline(
-            c, true, G.n_leaves, batch_leaves, true,
-            [&](int64_t o, int64_t m, void* stage) -> const void* {
-                const double t = now_s();
-                gather_leaves(static_cast<float*>(stage), G.leaf_ptrs + o, m);
-                copy_s += now_s() - t;
-                return stage;
-            },
-            [&](int64_t o, int64_t m, const void* res) -> int {
-                const double t = now_s();
-                rec.resize((size_t)m * REC_BYTES);
-                const uint8_t* idx = static_cast<const uint8_t*>(res);
-                unsigned char* p = rec.data();
-                for (int64_t l = 0; l < m; ++l, p += REC_BYTES) {
-                    std::memcpy(p, G.origins + 3 * (o + l), 12);
-                    std::memcpy(p + 12, idx + 64 * l, 64);
-                }
-                put(rec.data(), rec.size());
-                if (v2) {
-                    const float* e = c->bd_pin_cur;
-                    const unsigned char* pay = nullptr;
-                    int64_t pay_bytes = 0, at = 0;
-                    if (int frc = rs_fetch_payload(c, m, &pay, &pay_bytes)) return frc;
-                    const unsigned char* cls = pay + (size_t)c->rs_pin_leaves * 2048;   // the slot's classes lie behind its payload
-                    rrec.clear();
-                    for (int64_t l = 0; l < m; ++l) {
-                        if (cls[l] == VQHIP_RES_KEPT) {
-                            bst.max_err_kept = std::max(bst.max_err_kept, e[2 * l]);
-                            bst.sum_sq_kept += e[2 * l + 1];
-                            continue;
-                        }
-                        const int64_t sz = cls[l] == VQHIP_RES_RAW ? 2048 : 64 * (int64_t)cls[l];
-                        if (cls[l] > 16 && cls[l] != VQHIP_RES_RAW) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: class out of range");
-                        if (at + sz > pay_bytes) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: records exceed the payload");
-                        const uint32_t ri = (uint32_t)(o + l);
-                        const size_t w = rrec.size();
-                        rrec.resize(w + 5 + (size_t)sz);
-                        std::memcpy(&rrec[w], &ri, 4);
-                        rrec[w + 4] = cls[l];
-                        std::memcpy(&rrec[w + 5], pay + at, (size_t)sz);
-                        at += sz;
-                        ++grid_out;
-                        ++(cls[l] == VQHIP_RES_RAW ? rst.raw : rst.quantised);
-                    }
-                    if (at != pay_bytes) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: records do not fill the payload");
-                    rst.payload_bytes += pay_bytes;
-                    if (!rrec.empty()) rput(rrec.data(), rrec.size());
-                } else if (fr) {
-                    const float* e = c->bd_pin_cur;   // this chunk's {max |d|, sum d^2} per leaf
-                    for (int64_t l = 0; l < m; ++l) {
-                        if (!(e[2 * l] <= tol)) {
-                            const uint32_t ri = (uint32_t)(o + l);
-                            rput(&ri, 4);
-                            rput(G.leaf_ptrs[o + l], 2048);
-                            ++grid_out;
-                        } else {
-                            bst.max_err_kept = std::max(bst.max_err_kept, e[2 * l]);
-                            bst.sum_sq_kept += e[2 * l + 1];
-                        }
-                    }
-                }
-                write_s += now_s() - t;
-                if (rfail) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
-                return wfail ? fail(c, VQHIP_ERR_INVALID, "Failed to write to .vqvdb file.") : VQHIP_OK;
-            });
-        if (rc) return rc;
-        if (fr) {
-            if (std::fseek(fr, count_pos, SEEK_SET) != 0) rfail = true;
-            rput(&grid_out, 4);
-            if (std::fseek(fr, 0, SEEK_END) != 0) rfail = true;
-            if (rfail) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
-            bst.outliers += grid_out;
-        }
-        st.leaves += G.n_leaves;
-        st.copy_s += copy_s, st.read_s += write_s;
-    }
-    closer.f = nullptr;
-    if (std::fclose(f) != 0) return fail(c, VQHIP_ERR_INVALID, "Error closing the output file.");
-    if (fr) {
-        rcloser.f = nullptr;
-        if (std::fclose(fr) != 0) return fail(c, VQHIP_ERR_INVALID, "Error closing the residual file.");
-    }
-    st.wall_s = now_s() - t_start;
-    bst.leaves = st.leaves;
-    if (stats) *stats = st;
-    if (bstats) *bstats = bst;
-    if (rstats) *rstats = rst;
-    return VQHIP_OK;
-}
-
-int vqhip_compress_file(vqhip_codec* c, const char* path, const vqhip_grid_source* grids, int n_grids, int64_t batch_leaves, vqhip_stream_stats* stats)
-{
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file: null path or grid list");
-    return compress_file_impl(c, path, nullptr, grids, n_grids, batch_leaves, 0.0f, stats, nullptr);
-}
-
-int vqhip_compress_file_bounded(vqhip_codec* c, const char* path, const char* residual_path, const vqhip_grid_source* grids, int n_grids,
-                                int64_t batch_leaves, float tol, vqhip_stream_stats* stats, vqhip_bounded_stats* bstats)
-{
-    if (!c) return VQHIP_ERR_INVALID;
-    if (!path || !residual_path || !grids) return fail(c, VQHIP_ERR_INVALID, "compress_file_bounded: null path, residual path or grid list");
-    return compress_file_impl(c, path, residual_path, grids, n_grids, batch_leaves, tol, stats, bstats);
 }
 
 // ---- codebook training (stage 1): VectorQuantizerEMA.forward in training mode, VQVAE_v2.py:107-156 ----
@@ -3029,5 +2555,6 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_vec3_bounded.inc"
 #include "vq_bounded.inc"
 #include "vq_residual.inc"
+#include "vq_file.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"
