@@ -121,6 +121,10 @@ VEC3_PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_VEC3_PRECISION_*
 # every symbol include/vqvdb_hip_vec3_bounded.h declares (Vec3 error-bounded round trip; kept apart from the lists above)
 VEC3_BOUNDED_SYMBOLS = ["vqhip_vec3_roundtrip_device", "vqhip_vec3_select_outliers_device", "vqhip_vec3_compress_bounded"]
 VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
+# every symbol include/vqvdb_hip_vec3_residual.h declares (quantised residuals of the Vec3 handle; kept apart from the lists above)
+VEC3_RESIDUAL_SYMBOLS = ["vqhip_vec3_residual_encode_device", "vqhip_vec3_residual_apply_device", "vqhip_vec3_residual_compress",
+                         "vqhip_vec3_residual_decompress"]
+VEC3_RES_KEPT, VEC3_RES_RAW = 0xFFFE, 0xFFFF   # VQHIP_VEC3_RES_KEPT, VQHIP_VEC3_RES_RAW
 
 # every symbol include/vqvdb_hip_bounded.h declares (error-bounded compression on the scalar handle; kept apart from the lists above)
 BOUNDED_SYMBOLS = ["vqhip_roundtrip_device", "vqhip_select_outliers_device", "vqhip_compress_bounded", "vqhip_decompress_bounded",
@@ -292,6 +296,13 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_select_outliers_device.argtypes = [vp, vp, i64, cf, vp, vp, vp]
     lib.vqhip_vec3_compress_bounded.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp]
     for name in VEC3_BOUNDED_SYMBOLS:
+        getattr(lib, name).restype = ci
+    # include/vqvdb_hip_vec3_residual.h
+    lib.vqhip_vec3_residual_encode_device.argtypes = [vp, vp, vp, vp, i64, cf, vp, vp, vp, i64, vp]
+    lib.vqhip_vec3_residual_apply_device.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp]
+    lib.vqhip_vec3_residual_compress.argtypes = [vp, vp, i64, cf, vp, vp, vp, vp, vp]
+    lib.vqhip_vec3_residual_decompress.argtypes = [vp, vp, i64, cf, vp, vp, i64, vp]
+    for name in VEC3_RESIDUAL_SYMBOLS:
         getattr(lib, name).restype = ci
     # include/vqvdb_hip_bounded.h
     lib.vqhip_roundtrip_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -595,6 +606,80 @@ class HipVec3Codec:
             raise ValueError(f"outlier ids must be in [0, {indices.shape[0]})")
         out = self.decode(indices)
         out[ids] = raw
+        return out
+
+    # ---- quantised residuals: include/vqvdb_hip_vec3_residual.h ----
+    @staticmethod
+    def residual_record_sizes(leaf_code: np.ndarray) -> np.ndarray:
+        """int64 [n]: the record bytes of every code (0 for kept leaves, 6144 for raw ones, 64 * (b0 + b1 + b2) for the code
+        b0 | b1 << 5 | b2 << 10); a code that is neither a sentinel nor three widths of 0..16 with bit 15 clear is refused."""
+        c = np.asarray(leaf_code).astype(np.int64)
+        b = np.stack([c & 31, (c >> 5) & 31, (c >> 10) & 31], axis=-1)
+        sentinel = (c == VEC3_RES_KEPT) | (c == VEC3_RES_RAW)
+        if (~sentinel & ((c < 0) | (c >= 0x8000) | (b > 16).any(axis=-1))).any():
+            raise ValueError("leaf codes must be 0xFFFE (kept), 0xFFFF (raw) or b0 | b1 << 5 | b2 << 10 with every width in 0..16")
+        return np.where(c == VEC3_RES_KEPT, 0, np.where(c == VEC3_RES_RAW, 6144, 64 * b.sum(axis=-1)))
+
+    @classmethod
+    def check_residual(cls, n: int, leaf_code, payload):
+        """-> (code uint16 [n], payload uint8 [bytes]): one valid code per leaf and exactly their records."""
+        if not isinstance(leaf_code, np.ndarray) or leaf_code.dtype != np.uint16:
+            raise TypeError("leaf_code must be a uint16 numpy array")
+        lc = np.ascontiguousarray(leaf_code).reshape(-1)
+        if len(lc) != n:
+            raise ValueError(f"{n} leaves but {len(lc)} codes")
+        if isinstance(payload, (bytes, bytearray, memoryview)):
+            payload = np.frombuffer(payload, dtype=np.uint8)
+        if not isinstance(payload, np.ndarray) or payload.dtype != np.uint8:
+            raise TypeError("payload must be bytes or a uint8 numpy array")
+        pl = np.ascontiguousarray(payload).reshape(-1)
+        need = int(cls.residual_record_sizes(lc).sum())
+        if need != len(pl):
+            raise ValueError(f"the codes need {need} payload bytes, got {len(pl)}")
+        return lc, pl
+
+    def residual_encode_device(self, leaves_ptr: int, recon_ptr: int, leaf_err_ptr: int, n: int, tol: float, code_ptr: int, offsets_ptr: int,
+                               payload_ptr: int, payload_capacity: int, stream: int = 0):
+        """vqhip_vec3_residual_encode_device: codes [n] uint16, offsets [n+1] int64 (offsets[n] = the payload's bytes) and the payload."""
+        if n > 0 and not (leaves_ptr and recon_ptr and leaf_err_ptr and code_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, leaf_err, code and offsets are required")
+        if payload_capacity < 0:
+            raise ValueError("payload_capacity must be >= 0")
+        tol = self.check_tol(tol)
+        self._check(self._lib.vqhip_vec3_residual_encode_device(self._h, leaves_ptr, recon_ptr, leaf_err_ptr, n, tol, code_ptr, offsets_ptr,
+                                                                payload_ptr or None, payload_capacity, stream or None))
+
+    def residual_apply_device(self, leaves_ptr: int, n: int, tol: float, code_ptr: int, offsets_ptr: int, payload_ptr: int, stream: int = 0):
+        """vqhip_vec3_residual_apply_device: the decoded leaves at leaves_ptr corrected in place.  The device arrays are trusted."""
+        if n > 0 and not (leaves_ptr and code_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, code and offsets are required")
+        tol = self.check_tol(tol)
+        self._check(self._lib.vqhip_vec3_residual_apply_device(self._h, leaves_ptr, n, tol, code_ptr, offsets_ptr, payload_ptr or None,
+                                                               stream or None))
+
+    def compress_residual(self, leaves: np.ndarray, tol: float, return_leaf_err: bool = False):
+        """-> (indices [n,64], leaf_code uint16 [n], payload uint8 [bytes]): a leaf whose largest error is within ``tol`` is kept
+        (code 0xFFFE), any other is stored as its residual on a grid of 1.875 * tol with one bit width per channel (code
+        b0 | b1 << 5 | b2 << 10, 64 * (b0 + b1 + b2) bytes) or, where that cannot keep it within tol, raw (code 0xFFFF, 6144
+        bytes), so that decompress_residual in the same precision mode stays within tol on every value."""
+        leaves = self.check_leaves(leaves)
+        tol = self.check_tol(tol)
+        n = leaves.shape[0]
+        idx, err = np.empty((n, 64), dtype=np.uint16), np.empty((n, VEC3_ERR_FLOATS), dtype=np.float32)
+        lc, payload, nbytes = np.empty(n, dtype=np.uint16), np.empty(n * 6144, dtype=np.uint8), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_residual_compress(self._h, leaves.ctypes.data, n, tol, idx.ctypes.data, err.ctypes.data, lc.ctypes.data,
+                                                           payload.ctypes.data, ctypes.byref(nbytes)))
+        out = (idx, lc, payload[:nbytes.value].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def decompress_residual(self, indices: np.ndarray, tol: float, leaf_code, payload) -> np.ndarray:
+        """Decoded leaves [n,512,3] with the records of compress_residual (same ``tol``, same precision mode) applied."""
+        indices = self.check_indices(indices)
+        tol = self.check_tol(tol)
+        lc, pl = self.check_residual(indices.shape[0], leaf_code, payload)
+        out = np.empty((indices.shape[0], 512, 3), dtype=np.float32)
+        self._check(self._lib.vqhip_vec3_residual_decompress(self._h, indices.ctypes.data, indices.shape[0], tol, lc.ctypes.data, pl.ctypes.data,
+                                                             len(pl), out.ctypes.data))
         return out
 
     # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----

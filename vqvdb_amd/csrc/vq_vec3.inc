@@ -38,6 +38,13 @@ struct vqhip_vec3_codec {
     float* bd_err = nullptr;           // host entry point: leaf errors [bd_n][2]
     int64_t* bd_ids = nullptr;         // host entry point: outlier ids [bd_n], then their count
     int64_t bd_n = 0;
+    // quantised residuals (vq_vec3_residual.inc), host pair: one chunk's reconstruction, leaf errors, codes, offsets, payload
+    float* rs_recon = nullptr;         // [rs_n][512][3]
+    float* rs_err = nullptr;           // [rs_n][2]
+    uint16_t* rs_code = nullptr;       // [rs_n]
+    int64_t* rs_off = nullptr;         // [rs_n + 1]
+    uint8_t* rs_payload = nullptr;     // rs_n * 6144 bytes
+    int64_t rs_n = 0;
     struct Dbg {
         float* p = nullptr;
         int64_t cap = 0, n = 0;
@@ -573,6 +580,11 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     if (c->bd_scan) hipFree(c->bd_scan);
     if (c->bd_err) hipFree(c->bd_err);
     if (c->bd_ids) hipFree(c->bd_ids);
+    if (c->rs_recon) hipFree(c->rs_recon);
+    if (c->rs_err) hipFree(c->rs_err);
+    if (c->rs_code) hipFree(c->rs_code);
+    if (c->rs_off) hipFree(c->rs_off);
+    if (c->rs_payload) hipFree(c->rs_payload);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }

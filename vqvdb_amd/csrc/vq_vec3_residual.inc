@@ -1,0 +1,184 @@
+// vq_vec3_residual.inc — runtime of the Vec3 handle's quantised residuals (vqhip_vec3_residual_encode_device, _apply_device,
+// vqhip_vec3_residual_compress, _residual_decompress; include/vqvdb_hip_vec3_residual.h, DESIGN.md §18).  Part of
+// vq_runtime.hip's translation unit, after vq_residual.inc: the round trip and its leaf errors are vq_vec3_bounded.inc's,
+// unchanged; class_k, vqr::resid_scan_k, pack_k and apply_k follow them.
+
+#include "../../include/vqvdb_hip_vec3_residual.h"
+#include "vq_vec3_residual.h"
+
+static_assert(VQHIP_VEC3_RES_KEPT == v3r::CODE_KEPT && VQHIP_VEC3_RES_RAW == v3r::CODE_RAW, "the header's codes are the kernels'");
+
+namespace {
+
+inline unsigned v3r_grid(int64_t n)
+{
+    return (unsigned)((n + v3r::RES_WAVES - 1) / v3r::RES_WAVES);
+}
+
+inline bool v3r_code_ok(int code)
+{
+    return code == VQHIP_VEC3_RES_KEPT || code == VQHIP_VEC3_RES_RAW ||
+           (!(code & 0x8000) && (code & 31) <= 16 && ((code >> 5) & 31) <= 16 && ((code >> 10) & 31) <= 16);
+}
+
+inline int64_t v3r_record_size(int code)
+{
+    return code == VQHIP_VEC3_RES_KEPT ? 0 : code == VQHIP_VEC3_RES_RAW ? 6144 : 64 * (int64_t)((code & 31) + ((code >> 5) & 31) + ((code >> 10) & 31));
+}
+
+// class, scan, pack of n leaves: d_off[n] ends as the payload's size
+int v3r_encode(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, float tol, uint16_t* d_code,
+               int64_t* d_off, uint8_t* d_payload, int64_t capacity, hipStream_t s)
+{
+    hipLaunchKernelGGL(v3r::class_k, dim3(v3r_grid(n)), dim3(64 * v3r::RES_WAVES), 0, s, d_leaves, d_recon, d_err, n, tol, d_code, d_off);
+    hipLaunchKernelGGL(vqr::resid_scan_k, dim3(1), dim3(1024), 0, s, d_off, n);
+    hipLaunchKernelGGL(v3r::pack_k, dim3(v3r_grid(n)), dim3(64 * v3r::RES_WAVES), 0, s, d_leaves, d_recon, n, tol, d_code, d_off, d_payload, capacity);
+    return v3_launch_check(c, "vec3 residual_encode");
+}
+
+int v3r_apply(vqhip_vec3_codec* c, float* d_leaves, int64_t n, float tol, const uint16_t* d_code, const int64_t* d_off, const uint8_t* d_payload,
+              hipStream_t s)
+{
+    hipLaunchKernelGGL(v3r::apply_k, dim3(v3r_grid(n)), dim3(64 * v3r::RES_WAVES), 0, s, d_leaves, n, tol, d_code, d_off, d_payload);
+    return v3_launch_check(c, "vec3 residual_apply");
+}
+
+void v3r_free(vqhip_vec3_codec* c)
+{
+    if (c->rs_recon) hipFree(c->rs_recon), c->rs_recon = nullptr;
+    if (c->rs_err) hipFree(c->rs_err), c->rs_err = nullptr;
+    if (c->rs_code) hipFree(c->rs_code), c->rs_code = nullptr;
+    if (c->rs_off) hipFree(c->rs_off), c->rs_off = nullptr;
+    if (c->rs_payload) hipFree(c->rs_payload), c->rs_payload = nullptr;
+    c->rs_n = 0;
+}
+
+// host pair: reconstruction, leaf errors, codes, offsets and payload of one chunk
+int v3r_ensure_host(vqhip_vec3_codec* c, int64_t m)
+{
+    if (m <= c->rs_n) return VQHIP_OK;
+    v3r_free(c);
+    if (hipMalloc(&c->rs_recon, (size_t)m * 6144) != hipSuccess || hipMalloc(&c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float)) != hipSuccess ||
+        hipMalloc(&c->rs_code, (size_t)m * sizeof(uint16_t)) != hipSuccess || hipMalloc(&c->rs_off, (size_t)(m + 1) * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc(&c->rs_payload, (size_t)m * 6144) != hipSuccess) {
+        (void)hipGetLastError();
+        v3r_free(c);
+        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 residual: cannot allocate the record buffers of " + std::to_string(m) + " leaves");
+    }
+    c->rs_n = m;
+    return VQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vqhip_vec3_residual_encode_device(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, float tol,
+                                      uint16_t* d_code, int64_t* d_off, uint8_t* d_payload, int64_t capacity, void* stream)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_encode: n_leaves < 0");
+    if (n == 0) return VQHIP_OK;
+    if (capacity < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_encode: payload_capacity < 0");
+    if (!d_leaves || !d_recon || !d_err || !d_code || !d_off || (!d_payload && capacity > 0))
+        return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_encode: null pointer");
+    if (n > (int64_t(1) << 32)) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_encode: n_leaves exceeds 2^32");
+    HIPCHK(c, hipSetDevice(c->device));
+    return v3r_encode(c, d_leaves, d_recon, d_err, n, tol, d_code, d_off, d_payload, capacity, stream ? (hipStream_t)stream : c->stream);
+}
+
+int vqhip_vec3_residual_apply_device(vqhip_vec3_codec* c, float* d_leaves, int64_t n, float tol, const uint16_t* d_code, const int64_t* d_off,
+                                     const uint8_t* d_payload, void* stream)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_apply: n_leaves < 0");
+    if (n == 0) return VQHIP_OK;
+    if (!d_leaves || !d_code || !d_off) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_apply: null pointer");
+    if (n > (int64_t(1) << 32)) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 residual_apply: n_leaves exceeds 2^32");
+    HIPCHK(c, hipSetDevice(c->device));
+    return v3r_apply(c, d_leaves, n, tol, d_code, d_off, d_payload, stream ? (hipStream_t)stream : c->stream);
+}
+
+int vqhip_vec3_residual_compress(vqhip_vec3_codec* c, const float* leaves, int64_t n, float tol, uint16_t* indices, float* leaf_err,
+                                 uint16_t* leaf_code, uint8_t* payload, int64_t* payload_bytes)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 compress_residual: n_leaves < 0");
+    if (!payload_bytes) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 compress_residual: payload_bytes is NULL");
+    *payload_bytes = 0;
+    if (n == 0) return VQHIP_OK;
+    if (!leaves || !indices || !leaf_code || !payload) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 compress_residual: null pointer");
+    if (int rc = v3_prepare(c)) return rc;
+    int64_t total = 0;
+    for (int64_t o = 0; o < n; o += c->chunk) {
+        const int64_t m = std::min(c->chunk, n - o);
+        if (int rc = v3_ensure_io(c, m)) return rc;
+        if (int rc = v3r_ensure_host(c, m)) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->io_leaves, leaves + o * 1536, (size_t)m * 1536 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        int rc = v3e_roundtrip_chunk(c, c->io_leaves, m, c->io_idx, c->rs_recon, c->rs_err, c->stream);
+        if (!rc) rc = v3r_encode(c, c->io_leaves, c->rs_recon, c->rs_err, m, tol, c->rs_code, c->rs_off, c->rs_payload, m * 6144, c->stream);
+        if (rc) {
+            hipStreamSynchronize(c->stream);   // the copy above may still read the caller's leaves
+            return rc;
+        }
+        HIPCHK(c, hipMemcpyAsync(indices + o * 64, c->io_idx, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+        if (leaf_err)
+            HIPCHK(c, hipMemcpyAsync(leaf_err + o * VQHIP_VEC3_ERR_FLOATS, c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float),
+                                     hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(leaf_code + o, c->rs_code, (size_t)m * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+        int64_t bytes = 0;
+        HIPCHK(c, hipMemcpyAsync(&bytes, c->rs_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bytes < 0 || bytes > m * 6144) return v3_fail(c, VQHIP_ERR_DEVICE, "vec3 compress_residual: payload size out of range");
+        if (bytes > 0) HIPCHK(c, hipMemcpy(payload + total, c->rs_payload, (size_t)bytes, hipMemcpyDeviceToHost));
+        total += bytes;
+    }
+    *payload_bytes = total;
+    return VQHIP_OK;
+}
+
+int vqhip_vec3_residual_decompress(vqhip_vec3_codec* c, const uint16_t* indices, int64_t n, float tol, const uint16_t* leaf_code,
+                                   const uint8_t* payload, int64_t payload_bytes, float* leaves)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (n < 0 || payload_bytes < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decompress_residual: n_leaves < 0 or payload_bytes < 0");
+    if (n == 0) return VQHIP_OK;
+    if (!indices || !leaves || !leaf_code || (payload_bytes > 0 && !payload))
+        return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decompress_residual: null pointer");
+    int64_t need = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (!v3r_code_ok(leaf_code[i])) {
+            char hex[8];
+            std::snprintf(hex, sizeof hex, "0x%04X", (unsigned)leaf_code[i]);
+            return v3_fail(c, VQHIP_ERR_INVALID, std::string("vec3 decompress_residual: code ") + hex + " of leaf " + std::to_string(i) +
+                                                     " is neither 0xFFFE, 0xFFFF nor three widths of 0..16");
+        }
+        need += v3r_record_size(leaf_code[i]);
+    }
+    if (need != payload_bytes)
+        return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decompress_residual: the codes need " + std::to_string(need) + " payload bytes, the caller gives " +
+                                                 std::to_string(payload_bytes));
+    if (int rc = v3_prepare(c)) return rc;
+    std::vector<int64_t> off;
+    int64_t at = 0;
+    for (int64_t o = 0; o < n; o += c->chunk) {
+        const int64_t m = std::min(c->chunk, n - o);
+        if (int rc = v3_ensure_io(c, m)) return rc;
+        if (int rc = v3r_ensure_host(c, m)) return rc;
+        off.resize((size_t)m + 1);
+        off[0] = 0;
+        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + v3r_record_size(leaf_code[o + i]);
+        HIPCHK(c, hipMemcpy(c->io_idx, indices + o * 64, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->rs_code, leaf_code + o, (size_t)m * sizeof(uint16_t), hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(c->rs_off, off.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+        if (off[m] > 0) HIPCHK(c, hipMemcpy(c->rs_payload, payload + at, (size_t)off[m], hipMemcpyHostToDevice));
+        at += off[m];
+        if (int rc = v3_decode_mode(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
+        if (int rc = v3r_apply(c, c->io_leaves, m, tol, c->rs_code, c->rs_off, c->rs_payload, c->stream)) return rc;
+        HIPCHK(c, hipMemcpyAsync(leaves + o * 1536, c->io_leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return VQHIP_OK;
+}
+
+}  // extern "C"
