@@ -133,6 +133,10 @@ BOUNDED_SYMBOLS = ["vqhip_roundtrip_device", "vqhip_select_outliers_device", "vq
 RESIDUAL_SYMBOLS = ["vqhip_residual_encode_device", "vqhip_residual_apply_device", "vqhip_compress_residual", "vqhip_decompress_residual",
                     "vqhip_compress_file_residual", "vqhip_decompress_file_residual"]
 RES_KEPT, RES_RAW = 254, 255   # VQHIP_RES_KEPT, VQHIP_RES_RAW
+# every symbol include/vqvdb_hip_rate.h declares (size sweep and byte-budget compress of the scalar handle; kept apart from the lists above)
+RATE_SYMBOLS = ["vqhip_rate_payload_bytes", "vqhip_rate_sidecar_bytes", "vqhip_rate_sweep_device", "vqhip_rate_sweep", "vqhip_rate_sweep_file",
+                "vqhip_rate_compress_file"]
+RATE_MAX_TOLS, RATE_CLASSES = 64, 19   # VQHIP_RATE_MAX_TOLS, VQHIP_RATE_CLASSES: columns 0 .. 16 quantised, 17 raw, 18 kept
 ERR_FLOATS = 2   # VQHIP_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
@@ -324,6 +328,16 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_decompress_file_residual.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, i64, GRID_BEGIN_FN, LEAF_ALLOC_FN, vp, ctypes.POINTER(StreamStats)]
     for name in RESIDUAL_SYMBOLS:
         getattr(lib, name).restype = ci
+    # include/vqvdb_hip_rate.h
+    lib.vqhip_rate_payload_bytes.argtypes = [vp]
+    lib.vqhip_rate_sidecar_bytes.argtypes = [vp, ci]
+    lib.vqhip_rate_sweep_device.argtypes = [vp, vp, vp, vp, i64, vp, ci, vp, vp]
+    lib.vqhip_rate_sweep.argtypes = [vp, vp, i64, vp, ci, vp]
+    lib.vqhip_rate_sweep_file.argtypes = [vp, ctypes.POINTER(_GridSource), ci, i64, vp, ci, vp, ctypes.POINTER(StreamStats)]
+    lib.vqhip_rate_compress_file.argtypes = [vp, ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_GridSource), ci, i64, vp, ci, i64, vp, vp,
+                                             ctypes.POINTER(StreamStats), ctypes.POINTER(BoundedStats), ctypes.POINTER(ResidualStats)]
+    for name in RATE_SYMBOLS:
+        getattr(lib, name).restype = i64 if name.endswith("_bytes") else ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -1160,6 +1174,75 @@ class HipCodec:
         """decompress_file with the sidecar's records applied to every decoded batch on the GPU (vqhip_decompress_file_residual)."""
         return self._decompress_file(path, residual_path, batch_leaves, out, residual_version=2)
 
+    # ---- size sweep and byte-budget compress: include/vqvdb_hip_rate.h (DESIGN.md §19) ----
+    @classmethod
+    def check_tols(cls, tols) -> np.ndarray:
+        """1 .. 64 rungs, each a check_bound tolerance (a real number >= 0 or NaN, rounded down to float32) -> float32 [T]."""
+        if isinstance(tols, (str, bytes)) or not hasattr(tols, "__len__"):
+            raise TypeError("tols must be a sequence of real numbers")
+        if not 1 <= len(tols) <= RATE_MAX_TOLS:
+            raise ValueError(f"tols must hold 1..{RATE_MAX_TOLS} tolerances, got {len(tols)}")
+        return np.array([cls.check_bound(t) for t in tols], dtype=np.float32)
+
+    def rate_sweep_device(self, leaves_ptr: int, recon_ptr: int, leaf_err_ptr: int, n: int, tols, hist_ptr: int, stream: int = 0):
+        """vqhip_rate_sweep_device: ADDS the class histogram of n leaves at every rung to hist_ptr, a device buffer of
+        len(tols) x 19 int64 that the caller zeroes before the first call; nothing is read back or synchronised."""
+        tols = self.check_tols(tols)
+        if n > 0 and not (leaves_ptr and recon_ptr and leaf_err_ptr and hist_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, leaf_err and hist are required")
+        self._check(self._lib.vqhip_rate_sweep_device(self._h, leaves_ptr, recon_ptr, leaf_err_ptr, n, tols.ctypes.data, len(tols), hist_ptr,
+                                                      stream or None))
+
+    def rate_sweep(self, leaves: np.ndarray, tols) -> np.ndarray:
+        """-> hist int64 [T,19]: hist[t, k] leaves would get class k from compress_residual at tols[t] (k = 0 .. 16 quantised,
+        17 raw, 18 kept).  rate_payload_bytes / rate_sidecar_bytes turn a row into the bytes of that compress."""
+        leaves = self.check_leaves(leaves)
+        tols = self.check_tols(tols)
+        hist = np.empty((len(tols), RATE_CLASSES), dtype=np.int64)
+        self._check(self._lib.vqhip_rate_sweep(self._h, leaves.ctypes.data, leaves.shape[0], tols.ctypes.data, len(tols), hist.ctypes.data))
+        return hist
+
+    def rate_sweep_file(self, grids, tols, batch_leaves: int = 0):
+        """The sweep over compress_file's grid tuples, all grids in one histogram (vqhip_rate_sweep_file): no file is written.
+        Returns (hist int64 [T,19], stream statistics); row t predicts compress_file_residual at tols[t] to the byte."""
+        tols = self.check_tols(tols)
+        src, n_g, _keep = self._grid_sources(grids)
+        hist, st = np.empty((len(tols), RATE_CLASSES), dtype=np.int64), StreamStats()
+        self._check(self._lib.vqhip_rate_sweep_file(self._h, src, n_g, batch_leaves, tols.ctypes.data, len(tols), hist.ctypes.data, ctypes.byref(st)))
+        return hist, st.as_dict()
+
+    def rate_compress_file(self, path, residual_path, grids, tols, sidecar_budget: int, batch_leaves: int = 0, rounds: int = 1):
+        """compress_file_residual at the smallest of ``tols`` whose .vqres v2 sidecar has at most ``sidecar_budget`` bytes
+        (vqhip_rate_compress_file: one sweep over the grids, then the compress, so about twice compress_file_residual).  Raises,
+        before a file is opened, if no rung fits.  rounds > 1: before compressing, rounds - 1 further sweeps of 64 rungs, spaced
+        geometrically between the largest rung that did not fit and the chosen one, tighten the choice.  Returns (tol_used, hist
+        int64 [T,19] of the last ladder, stream, bounded and residual statistics of the compress)."""
+        tols = self.check_tols(tols)
+        if isinstance(sidecar_budget, bool) or not isinstance(sidecar_budget, (int, np.integer)):
+            raise TypeError(f"sidecar_budget must be an integer number of bytes, got {sidecar_budget!r}")
+        if sidecar_budget < 0:
+            raise ValueError(f"sidecar_budget must be >= 0, got {sidecar_budget}")
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or rounds < 1:
+            raise ValueError(f"rounds must be an integer >= 1, got {rounds!r}")
+        for _ in range(rounds - 1):
+            hist, _st = self.rate_sweep_file(grids, tols, batch_leaves)
+            fits = np.array([rate_sidecar_bytes(row, len(grids)) <= sidecar_budget for row in hist]) & ~np.isnan(tols)
+            if not fits.any():
+                break                                                # the library's call below refuses with both sizes
+            hi = tols[fits].min()
+            below = tols[~fits & (tols < hi)]
+            if not len(below) or not below.max() > 0 or not np.isfinite(hi):
+                break                                                # no interval to refine
+            tols = self.check_tols(list(np.geomspace(float(below.max()), float(hi), RATE_MAX_TOLS)))
+            tols[-1] = hi                                            # the rung known to fit, whatever the spacing rounds to
+        src, n_g, _keep = self._grid_sources(grids)
+        hist, used = np.empty((len(tols), RATE_CLASSES), dtype=np.int64), ctypes.c_float(0)
+        st, bst, rst = StreamStats(), BoundedStats(), ResidualStats()
+        self._check(self._lib.vqhip_rate_compress_file(self._h, os.fspath(path).encode(), os.fspath(residual_path).encode(), src, n_g, batch_leaves,
+                                                       tols.ctypes.data, len(tols), int(sidecar_budget), ctypes.byref(used), hist.ctypes.data,
+                                                       ctypes.byref(st), ctypes.byref(bst), ctypes.byref(rst)))
+        return used.value, hist, st.as_dict(), bst.as_dict(), rst.as_dict()
+
     # ---- codebook training (VectorQuantizerEMA in training mode; see vqvdb_amd/codebook_training.py) ----
     def train_begin(self, cluster_size: Optional[np.ndarray] = None, embed_avg: Optional[np.ndarray] = None):
         cs = None if cluster_size is None else np.ascontiguousarray(cluster_size, dtype=np.float32).reshape(256)
@@ -1295,6 +1378,25 @@ class HipCodec:
         out = (ctypes.c_int64 * 2)()
         self._check(self._lib.vqhip_selftest_mfma(self._h, out))
         return list(out)
+
+
+def _rate_row(row) -> np.ndarray:
+    r = np.asarray(row)
+    if r.shape != (RATE_CLASSES,) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"a histogram row holds {RATE_CLASSES} integers")
+    return np.ascontiguousarray(r, dtype=np.int64)
+
+
+def rate_payload_bytes(row) -> int:
+    """vqhip_rate_payload_bytes: the record bytes of a compress whose class histogram is ``row`` (int [19])."""
+    r = _rate_row(row)
+    return int(load_library().vqhip_rate_payload_bytes(r.ctypes.data))
+
+
+def rate_sidecar_bytes(row, n_grids: int) -> int:
+    """vqhip_rate_sidecar_bytes: the size of the .vqres v2 sidecar of ``n_grids`` grids whose class histogram is ``row``."""
+    r = _rate_row(row)
+    return int(load_library().vqhip_rate_sidecar_bytes(r.ctypes.data, int(n_grids)))
 
 
 class HipMultiCodec:

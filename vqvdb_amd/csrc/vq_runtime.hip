@@ -292,6 +292,8 @@ struct vqhip_codec {
     int64_t rs_leaves = 0;
     unsigned char* rs_pin[2] = {nullptr, nullptr};   // the file pair's pinned block: total, offsets, payload, classes
     int64_t rs_pin_leaves = 0;
+    // size sweep (vq_rate.inc): the histogram [64][19] of the host calls, allocated on first use, freed in vqhip_destroy
+    int64_t* rate_hist = nullptr;
 };
 
 namespace {
@@ -1943,6 +1945,7 @@ void vqhip_destroy(vqhip_codec* c)
     if (c->bd_idx) hipFree(c->bd_idx);
     if (c->bd_ids) hipFree(c->bd_ids);
     if (c->bd_scan) hipFree(c->bd_scan);
+    if (c->rate_hist) hipFree(c->rate_hist);
     for (int i = 0; i < 2; ++i) {
         if (c->bd_err[i]) hipFree(c->bd_err[i]);
         if (c->bd_pin_err[i]) hipHostFree(c->bd_pin_err[i]);
@@ -2557,5 +2560,6 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_residual.inc"
 #include "vq_vec3_residual.inc"
 #include "vq_file.inc"
+#include "vq_rate.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"
