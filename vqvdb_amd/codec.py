@@ -125,6 +125,11 @@ VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x
 VEC3_RESIDUAL_SYMBOLS = ["vqhip_vec3_residual_encode_device", "vqhip_vec3_residual_apply_device", "vqhip_vec3_residual_compress",
                          "vqhip_vec3_residual_decompress"]
 VEC3_RES_KEPT, VEC3_RES_RAW = 0xFFFE, 0xFFFF   # VQHIP_VEC3_RES_KEPT, VQHIP_VEC3_RES_RAW
+# every symbol include/vqvdb_hip_vec3_rate.h declares (size sweep and byte-budget compress of the Vec3 handle; kept apart from the lists above)
+VEC3_RATE_SYMBOLS = ["vqhip_vec3_rate_payload_bytes", "vqhip_vec3_rate_sweep_device", "vqhip_vec3_rate_sweep", "vqhip_vec3_rate_compress",
+                     "vqhip_vec3_rate_pick"]
+# VQHIP_VEC3_RATE_MAX_TOLS, VQHIP_VEC3_RATE_CLASSES: columns 0 .. 48 quantised by b0 + b1 + b2, 49 raw, 50 kept
+VEC3_RATE_MAX_TOLS, VEC3_RATE_CLASSES = 64, 51
 
 # every symbol include/vqvdb_hip_bounded.h declares (error-bounded compression on the scalar handle; kept apart from the lists above)
 BOUNDED_SYMBOLS = ["vqhip_roundtrip_device", "vqhip_select_outliers_device", "vqhip_compress_bounded", "vqhip_decompress_bounded",
@@ -308,6 +313,14 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_residual_decompress.argtypes = [vp, vp, i64, cf, vp, vp, i64, vp]
     for name in VEC3_RESIDUAL_SYMBOLS:
         getattr(lib, name).restype = ci
+    # include/vqvdb_hip_vec3_rate.h
+    lib.vqhip_vec3_rate_payload_bytes.argtypes = [vp]
+    lib.vqhip_vec3_rate_sweep_device.argtypes = [vp, vp, vp, vp, i64, vp, ci, vp, vp]
+    lib.vqhip_vec3_rate_sweep.argtypes = [vp, vp, i64, vp, ci, vp]
+    lib.vqhip_vec3_rate_compress.argtypes = [vp, vp, i64, vp, ci, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.vqhip_vec3_rate_pick.argtypes = [vp, vp, ci, i64]
+    for name in VEC3_RATE_SYMBOLS:
+        getattr(lib, name).restype = i64 if name.endswith("_bytes") else ci
     # include/vqvdb_hip_bounded.h
     lib.vqhip_roundtrip_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.vqhip_select_outliers_device.argtypes = [vp, vp, i64, cf, vp, vp, vp]
@@ -695,6 +708,67 @@ class HipVec3Codec:
         self._check(self._lib.vqhip_vec3_residual_decompress(self._h, indices.ctypes.data, indices.shape[0], tol, lc.ctypes.data, pl.ctypes.data,
                                                              len(pl), out.ctypes.data))
         return out
+
+    # ---- size sweep and byte-budget compress: include/vqvdb_hip_vec3_rate.h ----
+    @classmethod
+    def check_tols(cls, tols) -> np.ndarray:
+        """1 .. 64 rungs, each a real number >= 0 or NaN, rounded down to float32 by check_tol -> float32 [T]."""
+        if isinstance(tols, (str, bytes)) or not hasattr(tols, "__len__"):
+            raise TypeError("tols must be a sequence of real numbers")
+        if not 1 <= len(tols) <= VEC3_RATE_MAX_TOLS:
+            raise ValueError(f"tols must hold 1..{VEC3_RATE_MAX_TOLS} tolerances, got {len(tols)}")
+        out = np.array([cls.check_tol(t) for t in tols], dtype=np.float32)
+        if (out < 0).any():
+            raise ValueError(f"tol must be >= 0 (or NaN: every leaf raw), got {[t for t, v in zip(tols, out) if v < 0][0]!r}")
+        return out
+
+    @staticmethod
+    def rate_columns(leaf_code) -> np.ndarray:
+        """int64 [n]: the histogram column of every code of residual_encode_device / compress_residual: b0 + b1 + b2 for a
+        quantised leaf, 49 for a raw one, 50 for a kept one."""
+        c = np.asarray(leaf_code).astype(np.int64)
+        return np.where(c == VEC3_RES_KEPT, VEC3_RATE_CLASSES - 1,
+                        np.where(c == VEC3_RES_RAW, VEC3_RATE_CLASSES - 2, (c & 31) + ((c >> 5) & 31) + ((c >> 10) & 31)))
+
+    def rate_sweep_device(self, leaves_ptr: int, recon_ptr: int, leaf_err_ptr: int, n: int, tols, hist_ptr: int, stream: int = 0):
+        """vqhip_vec3_rate_sweep_device: ADDS the histogram of n leaves at every rung to hist_ptr, a device buffer of
+        len(tols) x 51 int64 that the caller zeroes before the first call; nothing is read back or synchronised."""
+        tols = self.check_tols(tols)
+        if n > 0 and not (leaves_ptr and recon_ptr and leaf_err_ptr and hist_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, leaf_err and hist are required")
+        self._check(self._lib.vqhip_vec3_rate_sweep_device(self._h, leaves_ptr, recon_ptr, leaf_err_ptr, n, tols.ctypes.data, len(tols), hist_ptr,
+                                                           stream or None))
+
+    def rate_sweep(self, leaves: np.ndarray, tols) -> np.ndarray:
+        """-> hist int64 [T,51]: hist[t, s] leaves would get a record of s = b0 + b1 + b2 planes (64 s bytes) from
+        compress_residual at tols[t] (s = 0 .. 48), hist[t, 49] a raw record, hist[t, 50] none (kept), in the handle's
+        precision mode.  vec3_rate_payload_bytes turns a row into the bytes of that compress."""
+        leaves = self.check_leaves(leaves)
+        tols = self.check_tols(tols)
+        hist = np.empty((len(tols), VEC3_RATE_CLASSES), dtype=np.int64)
+        self._check(self._lib.vqhip_vec3_rate_sweep(self._h, leaves.ctypes.data, leaves.shape[0], tols.ctypes.data, len(tols), hist.ctypes.data))
+        return hist
+
+    def rate_compress(self, leaves: np.ndarray, tols, payload_budget: int, return_leaf_err: bool = False):
+        """compress_residual at the smallest of ``tols`` whose payload has at most ``payload_budget`` bytes
+        (vqhip_vec3_rate_compress: one model round trip with the sweep behind it, then a decode and the encode of the records).
+        -> (tol_used, hist int64 [T,51], indices [n,64], leaf_code uint16 [n], payload uint8 [bytes][, leaf_err [n,2]]), the
+        last three or four as compress_residual(leaves, tol_used) returns them.  Raises RuntimeError if no rung fits."""
+        leaves = self.check_leaves(leaves)
+        tols = self.check_tols(tols)
+        if isinstance(payload_budget, bool) or not isinstance(payload_budget, (int, np.integer)):
+            raise TypeError(f"payload_budget must be an integer number of bytes, got {payload_budget!r}")
+        if payload_budget < 0:
+            raise ValueError(f"payload_budget must be >= 0, got {payload_budget}")
+        n = leaves.shape[0]
+        hist, used = np.empty((len(tols), VEC3_RATE_CLASSES), dtype=np.int64), ctypes.c_float(0)
+        idx, err = np.empty((n, 64), dtype=np.uint16), np.empty((n, VEC3_ERR_FLOATS), dtype=np.float32)
+        lc, payload, nbytes = np.empty(n, dtype=np.uint16), np.empty(n * 6144, dtype=np.uint8), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_rate_compress(self._h, leaves.ctypes.data, n, tols.ctypes.data, len(tols), int(payload_budget),
+                                                       ctypes.byref(used), hist.ctypes.data, idx.ctypes.data, err.ctypes.data, lc.ctypes.data,
+                                                       payload.ctypes.data, ctypes.byref(nbytes)))
+        out = (used.value, hist, idx, lc, payload[:nbytes.value].copy())
+        return out + (err,) if return_leaf_err else out
 
     # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----
     @staticmethod
@@ -1397,6 +1471,38 @@ def rate_sidecar_bytes(row, n_grids: int) -> int:
     """vqhip_rate_sidecar_bytes: the size of the .vqres v2 sidecar of ``n_grids`` grids whose class histogram is ``row``."""
     r = _rate_row(row)
     return int(load_library().vqhip_rate_sidecar_bytes(r.ctypes.data, int(n_grids)))
+
+
+def _vec3_rate_hist(hist, what="a histogram row") -> np.ndarray:
+    r = np.ascontiguousarray(hist)
+    if r.shape[-1:] != (VEC3_RATE_CLASSES,) or not np.issubdtype(r.dtype, np.integer):
+        raise ValueError(f"{what} holds {VEC3_RATE_CLASSES} integers")
+    return r.astype(np.int64)
+
+
+def vec3_rate_payload_bytes(row) -> int:
+    """vqhip_vec3_rate_payload_bytes: the record bytes of a Vec3 compress whose histogram row is ``row`` (int [51])."""
+    r = _vec3_rate_hist(row)
+    if r.ndim != 1:
+        raise ValueError(f"a histogram row holds {VEC3_RATE_CLASSES} integers")
+    return int(load_library().vqhip_vec3_rate_payload_bytes(r.ctypes.data))
+
+
+def vec3_rate_pick(hist, tols, payload_budget: int) -> int:
+    """vqhip_vec3_rate_pick: the index of the smallest tols[t] by value (NaN never) whose row of ``hist`` (int [T,51]) has a
+    payload of at most ``payload_budget`` bytes.  Raises ValueError if no rung fits."""
+    t = HipVec3Codec.check_tols(tols)
+    h = _vec3_rate_hist(hist, "every histogram row")
+    if h.shape != (len(t), VEC3_RATE_CLASSES):
+        raise ValueError(f"{len(t)} tolerances need a histogram of shape [{len(t)},{VEC3_RATE_CLASSES}], got {list(h.shape)}")
+    if isinstance(payload_budget, bool) or not isinstance(payload_budget, (int, np.integer)):
+        raise TypeError(f"payload_budget must be an integer number of bytes, got {payload_budget!r}")
+    if payload_budget < 0:
+        raise ValueError(f"payload_budget must be >= 0, got {payload_budget}")
+    best = int(load_library().vqhip_vec3_rate_pick(h.ctypes.data, t.ctypes.data, len(t), int(payload_budget)))
+    if best < 0:
+        raise ValueError(f"no rung fits {payload_budget} bytes")
+    return best
 
 
 class HipMultiCodec:

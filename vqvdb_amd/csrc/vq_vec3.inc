@@ -45,6 +45,8 @@ struct vqhip_vec3_codec {
     int64_t* rs_off = nullptr;         // [rs_n + 1]
     uint8_t* rs_payload = nullptr;     // rs_n * 6144 bytes
     int64_t rs_n = 0;
+    // size sweep (vq_vec3_rate.inc), host calls: the histogram [64][51], allocated on first use
+    int64_t* rate_hist = nullptr;
     struct Dbg {
         float* p = nullptr;
         int64_t cap = 0, n = 0;
@@ -585,6 +587,7 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     if (c->rs_code) hipFree(c->rs_code);
     if (c->rs_off) hipFree(c->rs_off);
     if (c->rs_payload) hipFree(c->rs_payload);
+    if (c->rate_hist) hipFree(c->rate_hist);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
