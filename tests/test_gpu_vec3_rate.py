@@ -140,6 +140,29 @@ def test_sweep_device_with_every_column_and_the_stride_loop(codec):
         assert np.array_equal(got[0], counts(code[:m])), m
 
 
+def test_sweep_device_on_unsorted_ladders_without_zero_and_with_a_nan_rung(codec):
+    """The shortcut "kept at every rung" beside finite rungs only, then switched off by a NaN rung.  Ladder A: unsorted, the
+    smallest rung (0.3) neither first nor last, no 0.0 and no NaN, so the leaves whose error is 0.25 take the shortcut and are
+    counted by lanes 0 .. 4; ladder B: A with a NaN rung in the middle."""
+    x, recon, err = t3t.every_column_leaves(TOL_S)
+    n = len(x)
+    forced = (np.arange(n) % 3 == 1) & np.isfinite(err[:, 0])
+    err[forced] = 0.25
+    assert n == 52 and forced.sum() >= 17 and np.isnan(err[:, 0]).any()
+    a = [TOL_S, float(F(0.75) * F(TOL_S)), float(F(4) * F(TOL_S)), float(F(0.3)), float("inf")]
+    b = a[:2] + [float("nan")] + a[2:]
+    assert min(a) == a[3] > 0.25
+    want_a, want_b = t3t.sweep(x, recon, err, a), t3t.sweep(x, recon, err, b)
+    assert (want_a[:, 50] >= forced.sum()).all() and want_a[3, 50] == forced.sum() < want_a[2, 50] < n   # the case tests something
+    dev = Resident(x, recon, err)
+    got_a, got_b = dev.sweep(codec, a).cpu().numpy(), dev.sweep(codec, b).cpu().numpy()
+    assert np.array_equal(got_a, want_a), got_a
+    assert np.array_equal(got_b, want_b), got_b
+    assert (got_a.sum(axis=1) == n).all() and (got_b.sum(axis=1) == n).all()
+    assert got_b[2, 49] == n                                         # the NaN rung: every leaf raw
+    assert np.array_equal(np.delete(got_b, 2, axis=0), got_a)        # ... and every other rung as without it
+
+
 def test_rate_sweep_on_host_leaves_at_two_chunk_sizes(codec, pack, leaves):
     _, err, rec = dev_roundtrip(codec, leaves)
     tols = ladder(err)

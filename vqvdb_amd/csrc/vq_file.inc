@@ -269,7 +269,7 @@ int write_sidecar_v2(vqhip_codec* c, SidecarOut& out, const PipeChunk& ch, const
             continue;
         }
         if (cls[l] > 16 && cls[l] != VQHIP_RES_RAW) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: class out of range");
-        const int64_t sz = rs_record_size(cls[l]);
+        const int64_t sz = vqr::record_size<1>(cls[l]);
         if (at + sz > pay_bytes) return fail(c, VQHIP_ERR_DEVICE, "compress_file_residual: records exceed the payload");
         const uint32_t ri = (uint32_t)(ch.o + l);
         const size_t w = out.rec.size();

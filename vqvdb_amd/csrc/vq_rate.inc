@@ -1,44 +1,69 @@
 // vq_rate.inc — runtime of the scalar handle's size sweep (vqhip_rate_sweep_device, _sweep, _sweep_file, _compress_file and the
 // two size helpers; include/vqvdb_hip_rate.h, DESIGN.md §19).  Part of vq_runtime.hip's translation unit, after vq_file.inc: the
-// round trip is vq_bounded.inc's, the file pipeline and compress_file_impl are vq_file.inc's, all unchanged; sweep_k of vq_rate.h
-// follows the round trip of every chunk and adds to one histogram that stays on the device until the call's end.
+// round trip is vq_bounded.inc's, the file pipeline and compress_file_impl are vq_file.inc's, all unchanged; sweep_k<1> of vq_rate.h
+// follows the round trip of every chunk and adds to one histogram that stays on the device until the call's end.  The helpers that
+// do not depend on the handle (rate_tols, rate_check_count, rate_check_tols, rate_payload, rate_pick) also serve vq_vec3_rate.inc.
 
 #include "../../include/vqvdb_hip_rate.h"
 #include "vq_rate.h"
 
-static_assert(VQHIP_RATE_MAX_TOLS == vqrate::RATE_MAX_TOLS && VQHIP_RATE_CLASSES == vqrate::RATE_CLASSES, "the header's table is the kernel's");
+static_assert(VQHIP_RATE_MAX_TOLS == vqrate::RATE_MAX_TOLS && VQHIP_RATE_CLASSES == vqrate::CLASSES<1>, "the header's table is the kernel's");
 
 namespace {
 
 constexpr size_t RATE_HIST_BYTES = (size_t)VQHIP_RATE_MAX_TOLS * VQHIP_RATE_CLASSES * sizeof(int64_t);
 
-inline int64_t rate_selected(const int64_t* row)
+// the payload of a compress whose histogram row this is: C channels per voxel
+template <int C>
+inline int64_t rate_payload(const int64_t* row)
 {
-    int64_t s = 0;
-    for (int b = 0; b <= vqrate::COL_RAW; ++b) s += row[b];
+    int64_t s = 2048 * C * row[vqrate::COL_RAW<C>];
+    for (int b = 0; b < vqrate::COL_RAW<C>; ++b) s += 64 * (int64_t)b * row[b];
     return s;
 }
 
-inline int64_t rate_payload(const int64_t* row)
+inline int64_t rate_selected(const int64_t* row)
 {
-    int64_t s = 2048 * row[vqrate::COL_RAW];
-    for (int b = 0; b <= 16; ++b) s += 64 * (int64_t)b * row[b];
+    int64_t s = 0;
+    for (int b = 0; b <= vqrate::COL_RAW<1>; ++b) s += row[b];
     return s;
 }
 
 inline int64_t rate_sidecar(const int64_t* row, int n_grids)
 {
-    return 11 + 4 * (int64_t)n_grids + 5 * rate_selected(row) + rate_payload(row);
+    return 11 + 4 * (int64_t)n_grids + 5 * rate_selected(row) + rate_payload<1>(row);
 }
 
-int rate_check_count(vqhip_codec* c, const char* what, int n_tols)
+// the smallest rung by value whose row of hist [n_tols][16 C + 3] has a size within the budget; no order of the rungs and no
+// monotone sizes are assumed, NaN never compares as smaller.  *smallest: the smallest size of the rungs that are not NaN, -1 if
+// there is none
+template <int C, typename Size>
+int rate_pick(const int64_t* hist, const float* tols, int n_tols, int64_t budget, Size size_of_row, int64_t* smallest)
 {
-    if (n_tols < 1 || n_tols > VQHIP_RATE_MAX_TOLS)
-        return fail(c, VQHIP_ERR_INVALID, std::string(what) + ": n_tols " + std::to_string(n_tols) + " is not in 1.." + std::to_string(VQHIP_RATE_MAX_TOLS));
+    int best = -1;
+    int64_t least = -1;
+    for (int t = 0; t < n_tols; ++t) {
+        if (tols[t] != tols[t]) continue;
+        const int64_t bytes = size_of_row(hist + (size_t)t * vqrate::CLASSES<C>);
+        if (least < 0 || bytes < least) least = bytes;
+        if (bytes <= budget && (best < 0 || tols[t] < tols[best])) best = t;
+    }
+    if (smallest) *smallest = least;
+    return best;
+}
+
+inline int fail(vqhip_vec3_codec* c, int code, const std::string& msg) { return v3_fail(c, code, msg); }
+
+template <typename Handle>
+int rate_check_count(Handle* c, const char* what, int n_tols)
+{
+    if (n_tols < 1 || n_tols > vqrate::RATE_MAX_TOLS)
+        return fail(c, VQHIP_ERR_INVALID, std::string(what) + ": n_tols " + std::to_string(n_tols) + " is not in 1.." + std::to_string(vqrate::RATE_MAX_TOLS));
     return VQHIP_OK;
 }
 
-int rate_check_tols(vqhip_codec* c, const char* what, const float* tols, int n_tols)
+template <typename Handle>
+int rate_check_tols(Handle* c, const char* what, const float* tols, int n_tols)
 {
     if (int rc = rate_check_count(c, what, n_tols)) return rc;
     return tols ? VQHIP_OK : fail(c, VQHIP_ERR_INVALID, std::string(what) + ": tols is NULL");
@@ -60,7 +85,7 @@ int rate_sweep(vqhip_codec* c, const float* d_leaves, const float* d_recon, cons
     const unsigned grid = (unsigned)std::min<int64_t>((n + vqrate::RATE_WAVES - 1) / vqrate::RATE_WAVES, vqrate::RATE_MAX_GRID);
     Launcher L{c, s, n};
     L.run("rate_sweep", [&] {
-        hipLaunchKernelGGL(vqrate::sweep_k, dim3(grid), dim3(64 * vqrate::RATE_WAVES), 0, s, d_leaves, d_recon, d_err, n, T,
+        hipLaunchKernelGGL(vqrate::sweep_k<1>, dim3(grid), dim3(64 * vqrate::RATE_WAVES), 0, s, d_leaves, d_recon, d_err, n, T,
                            reinterpret_cast<unsigned long long*>(d_hist));
     });
     return L.rc;
@@ -142,7 +167,7 @@ extern "C" {
 
 int64_t vqhip_rate_payload_bytes(const int64_t* hist_row)
 {
-    return hist_row ? rate_payload(hist_row) : -1;
+    return hist_row ? rate_payload<1>(hist_row) : -1;
 }
 
 int64_t vqhip_rate_sidecar_bytes(const int64_t* hist_row, int n_grids)
@@ -210,15 +235,8 @@ int vqhip_rate_compress_file(vqhip_codec* c, const char* path, const char* resid
     int64_t table[VQHIP_RATE_MAX_TOLS * VQHIP_RATE_CLASSES];
     if (int rc = sweep_file_impl(c, grids, n_grids, batch_leaves, tols, n_tols, table, nullptr)) return rc;
     if (hist) std::memcpy(hist, table, (size_t)n_tols * VQHIP_RATE_CLASSES * sizeof(int64_t));
-    // the smallest rung by value that fits; no order of the rungs and no monotone sizes are assumed, NaN never compares as smaller
-    int best = -1;
     int64_t smallest = -1;
-    for (int t = 0; t < n_tols; ++t) {
-        if (tols[t] != tols[t]) continue;
-        const int64_t bytes = rate_sidecar(table + (size_t)t * VQHIP_RATE_CLASSES, n_grids);
-        if (smallest < 0 || bytes < smallest) smallest = bytes;
-        if (bytes <= sidecar_budget && (best < 0 || tols[t] < tols[best])) best = t;
-    }
+    const int best = rate_pick<1>(table, tols, n_tols, sidecar_budget, [&](const int64_t* row) { return rate_sidecar(row, n_grids); }, &smallest);
     if (best < 0) {
         if (smallest < 0) return fail(c, VQHIP_ERR_INVALID, "rate_compress_file: every rung is NaN, none can be chosen");
         return fail(c, VQHIP_ERR_INVALID, "rate_compress_file: the smallest sidecar of the " + std::to_string(n_tols) + " rungs has " +

@@ -1,13 +1,13 @@
 // vq_residual.inc — runtime of the scalar handle's quantised residuals (vqhip_residual_encode_device, _apply_device,
 // _compress_residual, _decompress_residual and the file pair; include/vqvdb_hip_residual.h, DESIGN.md §17).  Part of
 // vq_runtime.hip's translation unit, after vq_bounded.inc: the round trip and its leaf errors are that file's, unchanged; the
-// four kernels of vq_residual.h follow them.  The file pair runs compress_file_impl / decompress_file_impl of vq_file.inc,
+// four kernels of vq_residual.h (C = 1) follow them.  The file pair runs compress_file_impl / decompress_file_impl of vq_file.inc,
 // which hang rs_encode_stage / rs_decode_stage below behind every chunk of the host pipeline.
 
 #include "../../include/vqvdb_hip_residual.h"
 #include "vq_residual.h"
 
-static_assert(VQHIP_RES_KEPT == vqr::CLASS_KEPT && VQHIP_RES_RAW == vqr::CLASS_RAW, "the header's classes are the kernels'");
+static_assert(VQHIP_RES_KEPT == vqr::Format<1>::KEPT && VQHIP_RES_RAW == vqr::Format<1>::RAW, "the header's classes are the kernels'");
 
 namespace {
 
@@ -16,27 +16,17 @@ inline unsigned rs_grid(int64_t n)
     return (unsigned)((n + vqr::RES_WAVES - 1) / vqr::RES_WAVES);
 }
 
-inline bool rs_class_ok(int cls)
-{
-    return cls <= 16 || cls == VQHIP_RES_KEPT || cls == VQHIP_RES_RAW;
-}
-
-inline int64_t rs_record_size(int cls)
-{
-    return cls == VQHIP_RES_KEPT ? 0 : cls == VQHIP_RES_RAW ? 2048 : 64 * (int64_t)cls;
-}
-
 // class, scan, pack of n leaves: d_off[n] ends as the payload's size
 int rs_encode(vqhip_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, float tol, uint8_t* d_class, int64_t* d_off,
               uint8_t* d_payload, int64_t capacity, hipStream_t s)
 {
     Launcher L{c, s, n};
     L.run("residual_class", [&] {
-        hipLaunchKernelGGL(vqr::resid_class_k, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, d_err, n, tol, d_class, d_off);
+        hipLaunchKernelGGL(vqr::resid_class_k<1>, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, d_err, n, tol, d_class, d_off);
     });
     L.run("residual_scan", [&] { hipLaunchKernelGGL(vqr::resid_scan_k, dim3(1), dim3(1024), 0, s, d_off, n); });
     L.run("residual_pack", [&] {
-        hipLaunchKernelGGL(vqr::resid_pack_k, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, n, tol, d_class, d_off, d_payload,
+        hipLaunchKernelGGL(vqr::resid_pack_k<1>, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, n, tol, d_class, d_off, d_payload,
                            capacity);
     });
     return L.rc;
@@ -46,7 +36,7 @@ int rs_apply(vqhip_codec* c, float* d_leaves, int64_t n, float tol, const uint8_
 {
     Launcher L{c, s, n};
     L.run("residual_apply", [&] {
-        hipLaunchKernelGGL(vqr::resid_apply_k, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, n, tol, d_class, d_off, d_payload);
+        hipLaunchKernelGGL(vqr::resid_apply_k<1>, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, n, tol, d_class, d_off, d_payload);
     });
     return L.rc;
 }
@@ -131,7 +121,7 @@ int rs_upload_apply(vqhip_codec* c, int64_t m, float tol, int slot, hipStream_t 
     const unsigned char* cls = rs_pin_class(c, slot);
     int64_t* off = rs_pin_off(c, slot);
     off[0] = 0;
-    for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + rs_record_size(cls[i]);
+    for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + vqr::record_size<1>(cls[i]);
     const int64_t total = off[m];
     HIPCHK(c, hipMemcpyAsync(c->rs_class[slot], rs_pin_class(c, slot), (size_t)m, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipMemcpyAsync(c->rs_off[slot], rs_pin_off(c, slot), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -173,7 +163,7 @@ struct ResidualWalk {
                 if (v2) cls = eh[4];
             }
             if (pending >= o + m) break;   // a later chunk's leaf (earlier ones went with their chunk: pending >= o)
-            const size_t sz = (size_t)rs_record_size(cls);
+            const size_t sz = (size_t)vqr::record_size<1>(cls);
             void* to = dst(pending - o, cls);   // also for a class of no bytes
             if (sz && std::fread(to, 1, sz, fr) != sz) return fail(c, VQHIP_ERR_INVALID, "Residual file truncated: incomplete leaf entry.");
             prev = pending, pending = -1, --left;
@@ -195,7 +185,7 @@ PipeStage rs_decode_stage(vqhip_codec* c, float tol, ResidualWalk* walk)
                     if (!any) std::memset(cls, VQHIP_RES_KEPT, (size_t)m), any = true;
                     cls[l] = (unsigned char)k;
                     unsigned char* at = pay;
-                    pay += rs_record_size(k);
+                    pay += vqr::record_size<1>(k);
                     return at;
                 });
                 return rc || !any ? rc : rs_upload_apply(c, m, tol, slot, s);
@@ -280,10 +270,10 @@ int vqhip_decompress_residual(vqhip_codec* c, const uint8_t* indices, int64_t n,
     if (!indices || !leaves || !leaf_class || (payload_bytes > 0 && !payload)) return fail(c, VQHIP_ERR_INVALID, "decompress_residual: null pointer");
     int64_t need = 0;
     for (int64_t i = 0; i < n; ++i) {
-        if (!rs_class_ok(leaf_class[i]))
+        if (!vqr::code_ok<1>(leaf_class[i]))
             return fail(c, VQHIP_ERR_INVALID, "decompress_residual: class " + std::to_string((int)leaf_class[i]) + " of leaf " + std::to_string(i) +
                                                   " is not 0..16, 254 or 255");
-        need += rs_record_size(leaf_class[i]);
+        need += vqr::record_size<1>(leaf_class[i]);
     }
     if (need != payload_bytes)
         return fail(c, VQHIP_ERR_INVALID, "decompress_residual: the classes need " + std::to_string(need) + " payload bytes, the caller gives " +
@@ -297,7 +287,7 @@ int vqhip_decompress_residual(vqhip_codec* c, const uint8_t* indices, int64_t n,
         if (int rc = rs_ensure(c, m, false)) return rc;
         off.resize((size_t)m + 1);
         off[0] = 0;
-        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + rs_record_size(leaf_class[o + i]);
+        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + vqr::record_size<1>(leaf_class[o + i]);
         HIPCHK(c, hipMemcpy(c->dev_idx[0], indices + o * 64, (size_t)m * 64, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->rs_class[0], leaf_class + o, (size_t)m, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->rs_off[0], off.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));

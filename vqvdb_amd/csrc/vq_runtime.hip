@@ -2559,8 +2559,8 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_bounded.inc"
 #include "vq_residual.inc"
 #include "vq_vec3_residual.inc"
-#include "vq_vec3_rate.inc"
 #include "vq_file.inc"
 #include "vq_rate.inc"
+#include "vq_vec3_rate.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"

@@ -1,69 +1,25 @@
 // vq_vec3_rate.inc — runtime of the Vec3 handle's size sweep (vqhip_vec3_rate_payload_bytes, _sweep_device, _sweep, _compress,
-// _pick; include/vqvdb_hip_vec3_rate.h, DESIGN.md §20).  Part of vq_runtime.hip's translation unit, after vq_vec3_residual.inc:
-// the round trip is vq_vec3_bounded.inc's, the encode of the records vq_vec3_residual.inc's, both unchanged; sweep_k of
-// vq_vec3_rate.h follows the round trip of every chunk and adds to one histogram that stays on the device until the call's end.
+// _pick; include/vqvdb_hip_vec3_rate.h, DESIGN.md §20).  Part of vq_runtime.hip's translation unit, after vq_vec3_residual.inc
+// and vq_rate.inc: the round trip is vq_vec3_bounded.inc's, the encode of the records and the chunk tail vq_vec3_residual.inc's,
+// the ladder checks, rate_payload and rate_pick vq_rate.inc's; sweep_k<3> of vq_rate.h follows the round trip of every chunk and
+// adds to one histogram that stays on the device until the call's end.
 
 #include "../../include/vqvdb_hip_vec3_rate.h"
-#include "vq_vec3_rate.h"
+#include "vq_rate.h"
 
-static_assert(VQHIP_VEC3_RATE_MAX_TOLS == v3rate::RATE_MAX_TOLS && VQHIP_VEC3_RATE_CLASSES == v3rate::RATE_CLASSES, "the header's table is the kernel's");
+static_assert(VQHIP_VEC3_RATE_MAX_TOLS == vqrate::RATE_MAX_TOLS && VQHIP_VEC3_RATE_CLASSES == vqrate::CLASSES<3>, "the header's table is the kernel's");
 
 namespace {
 
 constexpr size_t V3RATE_ROW_BYTES = (size_t)VQHIP_VEC3_RATE_CLASSES * sizeof(int64_t);
 constexpr size_t V3RATE_HIST_BYTES = (size_t)VQHIP_VEC3_RATE_MAX_TOLS * V3RATE_ROW_BYTES;
 
-inline int64_t v3rate_payload(const int64_t* row)
-{
-    int64_t s = 6144 * row[v3rate::COL_RAW];
-    for (int b = 0; b < v3rate::COL_RAW; ++b) s += 64 * (int64_t)b * row[b];
-    return s;
-}
-
-// the smallest rung by value that fits; no order of the rungs and no monotone sizes are assumed, NaN never compares as smaller.
-// *smallest: the smallest payload of the rungs that are not NaN, -1 if there is none
-int v3rate_pick(const int64_t* hist, const float* tols, int n_tols, int64_t budget, int64_t* smallest)
-{
-    int best = -1;
-    int64_t least = -1;
-    for (int t = 0; t < n_tols; ++t) {
-        if (tols[t] != tols[t]) continue;
-        const int64_t bytes = v3rate_payload(hist + (size_t)t * VQHIP_VEC3_RATE_CLASSES);
-        if (least < 0 || bytes < least) least = bytes;
-        if (bytes <= budget && (best < 0 || tols[t] < tols[best])) best = t;
-    }
-    if (smallest) *smallest = least;
-    return best;
-}
-
-int v3rate_check_count(vqhip_vec3_codec* c, const char* what, int n_tols)
-{
-    if (n_tols < 1 || n_tols > VQHIP_VEC3_RATE_MAX_TOLS)
-        return v3_fail(c, VQHIP_ERR_INVALID, std::string(what) + ": n_tols " + std::to_string(n_tols) + " is not in 1.." + std::to_string(VQHIP_VEC3_RATE_MAX_TOLS));
-    return VQHIP_OK;
-}
-
-int v3rate_check_tols(vqhip_vec3_codec* c, const char* what, const float* tols, int n_tols)
-{
-    if (int rc = v3rate_check_count(c, what, n_tols)) return rc;
-    return tols ? VQHIP_OK : v3_fail(c, VQHIP_ERR_INVALID, std::string(what) + ": tols is NULL");
-}
-
-v3rate::Tols v3rate_tols(const float* tols, int n_tols)
-{
-    v3rate::Tols T;
-    std::memset(&T, 0, sizeof T);
-    T.count = n_tols;
-    std::memcpy(T.t, tols, (size_t)n_tols * sizeof(float));
-    return T;
-}
-
 // the histogram of n leaves added to d_hist
-int v3rate_sweep(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, const v3rate::Tols& T, int64_t* d_hist,
+int v3rate_sweep(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, const vqrate::Tols& T, int64_t* d_hist,
                  hipStream_t s)
 {
-    const unsigned grid = (unsigned)std::min<int64_t>((n + v3rate::RATE_WAVES - 1) / v3rate::RATE_WAVES, v3rate::RATE_MAX_GRID);
-    hipLaunchKernelGGL(v3rate::sweep_k, dim3(grid), dim3(64 * v3rate::RATE_WAVES), 0, s, d_leaves, d_recon, d_err, n, T,
+    const unsigned grid = (unsigned)std::min<int64_t>((n + vqrate::RATE_WAVES - 1) / vqrate::RATE_WAVES, vqrate::RATE_MAX_GRID);
+    hipLaunchKernelGGL(vqrate::sweep_k<3>, dim3(grid), dim3(64 * vqrate::RATE_WAVES), 0, s, d_leaves, d_recon, d_err, n, T,
                        reinterpret_cast<unsigned long long*>(d_hist));
     return v3_launch_check(c, "vec3 rate_sweep");
 }
@@ -91,7 +47,7 @@ int v3rate_sweep_host(vqhip_vec3_codec* c, const float* leaves, int64_t n, const
 {
     if (int rc = v3_prepare(c)) return rc;
     if (int rc = v3rate_begin(c)) return rc;
-    const v3rate::Tols T = v3rate_tols(tols, n_tols);
+    const vqrate::Tols T = rate_tols(tols, n_tols);
     for (int64_t o = 0; o < n; o += c->chunk) {
         const int64_t m = std::min(c->chunk, n - o);
         if (int rc = v3_ensure_io(c, m)) return rc;
@@ -118,13 +74,13 @@ extern "C" {
 
 int64_t vqhip_vec3_rate_payload_bytes(const int64_t* hist_row)
 {
-    return hist_row ? v3rate_payload(hist_row) : -1;
+    return hist_row ? rate_payload<3>(hist_row) : -1;
 }
 
 int vqhip_vec3_rate_pick(const int64_t* hist, const float* tols, int n_tols, int64_t payload_budget)
 {
     if (!hist || !tols || n_tols < 1 || n_tols > VQHIP_VEC3_RATE_MAX_TOLS || payload_budget < 0) return -1;
-    return v3rate_pick(hist, tols, n_tols, payload_budget, nullptr);
+    return rate_pick<3>(hist, tols, n_tols, payload_budget, rate_payload<3>, nullptr);
 }
 
 int vqhip_vec3_rate_sweep_device(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, const float* tols,
@@ -132,19 +88,19 @@ int vqhip_vec3_rate_sweep_device(vqhip_vec3_codec* c, const float* d_leaves, con
 {
     if (!c) return VQHIP_ERR_INVALID;
     if (n < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_sweep: n_leaves < 0");
-    if (int rc = v3rate_check_count(c, "vec3 rate_sweep", n_tols)) return rc;
+    if (int rc = rate_check_count(c, "vec3 rate_sweep", n_tols)) return rc;
     if (n == 0) return VQHIP_OK;
     if (!d_leaves || !d_recon || !d_err || !tols || !d_hist) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_sweep: null pointer");
     if (n > (int64_t(1) << 32)) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_sweep: n_leaves exceeds 2^32");
     HIPCHK(c, hipSetDevice(c->device));
-    return v3rate_sweep(c, d_leaves, d_recon, d_err, n, v3rate_tols(tols, n_tols), d_hist, stream ? (hipStream_t)stream : c->stream);
+    return v3rate_sweep(c, d_leaves, d_recon, d_err, n, rate_tols(tols, n_tols), d_hist, stream ? (hipStream_t)stream : c->stream);
 }
 
 int vqhip_vec3_rate_sweep(vqhip_vec3_codec* c, const float* leaves, int64_t n, const float* tols, int n_tols, int64_t* hist)
 {
     if (!c) return VQHIP_ERR_INVALID;
     if (n < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_sweep: n_leaves < 0");
-    if (int rc = v3rate_check_tols(c, "vec3 rate_sweep", tols, n_tols)) return rc;
+    if (int rc = rate_check_tols(c, "vec3 rate_sweep", tols, n_tols)) return rc;
     if (!hist) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_sweep: hist is NULL");
     std::memset(hist, 0, (size_t)n_tols * V3RATE_ROW_BYTES);
     if (n == 0) return VQHIP_OK;
@@ -160,12 +116,12 @@ int vqhip_vec3_rate_compress(vqhip_vec3_codec* c, const float* leaves, int64_t n
     if (!tol_used || !payload_bytes) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_compress: tol_used or payload_bytes is NULL");
     *payload_bytes = 0;
     if (payload_budget < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_compress: payload_budget < 0");
-    if (int rc = v3rate_check_tols(c, "vec3 rate_compress", tols, n_tols)) return rc;
+    if (int rc = rate_check_tols(c, "vec3 rate_compress", tols, n_tols)) return rc;
     int64_t table[VQHIP_VEC3_RATE_MAX_TOLS * VQHIP_VEC3_RATE_CLASSES];
     std::memset(table, 0, (size_t)n_tols * V3RATE_ROW_BYTES);
     if (n == 0) {   // every rung needs 0 bytes: the smallest that is not NaN, if there is one
         if (hist) std::memcpy(hist, table, (size_t)n_tols * V3RATE_ROW_BYTES);
-        const int best = v3rate_pick(table, tols, n_tols, payload_budget, nullptr);
+        const int best = rate_pick<3>(table, tols, n_tols, payload_budget, rate_payload<3>, nullptr);
         if (best >= 0) *tol_used = tols[best];
         return VQHIP_OK;
     }
@@ -179,7 +135,7 @@ int vqhip_vec3_rate_compress(vqhip_vec3_codec* c, const float* leaves, int64_t n
     if (int rc = v3rate_sweep_host(c, leaves, n, tols, n_tols, table, indices, leaf_err)) return rc;
     if (hist) std::memcpy(hist, table, (size_t)n_tols * V3RATE_ROW_BYTES);
     int64_t smallest = -1;
-    const int best = v3rate_pick(table, tols, n_tols, payload_budget, &smallest);
+    const int best = rate_pick<3>(table, tols, n_tols, payload_budget, rate_payload<3>, &smallest);
     if (best < 0) {
         if (smallest < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_compress: every rung is NaN, none can be chosen");
         return v3_fail(c, VQHIP_ERR_INVALID, "vec3 rate_compress: the smallest payload of the " + std::to_string(n_tols) + " rungs has " +
@@ -203,17 +159,11 @@ int vqhip_vec3_rate_compress(vqhip_vec3_codec* c, const float* leaves, int64_t n
             hipStreamSynchronize(c->stream);   // the copies above may still read the caller's arrays
             return rc;
         }
-        HIPCHK(c, hipMemcpyAsync(leaf_code + o, c->rs_code, (size_t)m * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-        int64_t bytes = 0;
-        HIPCHK(c, hipMemcpyAsync(&bytes, c->rs_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (bytes < 0 || bytes > m * 6144) return v3_fail(c, VQHIP_ERR_DEVICE, "vec3 rate_compress: payload size out of range");
-        if (bytes > 0) HIPCHK(c, hipMemcpy(payload + total, c->rs_payload, (size_t)bytes, hipMemcpyDeviceToHost));
-        total += bytes;
+        if ((rc = v3r_fetch_chunk(c, "vec3 rate_compress", o, m, leaf_code, payload, &total))) return rc;
     }
-    if (total != v3rate_payload(table + (size_t)best * VQHIP_VEC3_RATE_CLASSES))
+    if (total != rate_payload<3>(table + (size_t)best * VQHIP_VEC3_RATE_CLASSES))
         return v3_fail(c, VQHIP_ERR_DEVICE, "vec3 rate_compress: the payload has " + std::to_string(total) + " bytes, the histogram predicted " +
-                                                std::to_string(v3rate_payload(table + (size_t)best * VQHIP_VEC3_RATE_CLASSES)));
+                                                std::to_string(rate_payload<3>(table + (size_t)best * VQHIP_VEC3_RATE_CLASSES)));
     *payload_bytes = total;
     return VQHIP_OK;
 }

@@ -1,45 +1,29 @@
 // vq_vec3_residual.inc — runtime of the Vec3 handle's quantised residuals (vqhip_vec3_residual_encode_device, _apply_device,
 // vqhip_vec3_residual_compress, _residual_decompress; include/vqvdb_hip_vec3_residual.h, DESIGN.md §18).  Part of
 // vq_runtime.hip's translation unit, after vq_residual.inc: the round trip and its leaf errors are vq_vec3_bounded.inc's,
-// unchanged; class_k, vqr::resid_scan_k, pack_k and apply_k follow them.
+// unchanged; the four kernels of vq_residual.h (C = 3) follow them.
 
 #include "../../include/vqvdb_hip_vec3_residual.h"
-#include "vq_vec3_residual.h"
+#include "vq_residual.h"
 
-static_assert(VQHIP_VEC3_RES_KEPT == v3r::CODE_KEPT && VQHIP_VEC3_RES_RAW == v3r::CODE_RAW, "the header's codes are the kernels'");
+static_assert(VQHIP_VEC3_RES_KEPT == vqr::Format<3>::KEPT && VQHIP_VEC3_RES_RAW == vqr::Format<3>::RAW, "the header's codes are the kernels'");
 
 namespace {
-
-inline unsigned v3r_grid(int64_t n)
-{
-    return (unsigned)((n + v3r::RES_WAVES - 1) / v3r::RES_WAVES);
-}
-
-inline bool v3r_code_ok(int code)
-{
-    return code == VQHIP_VEC3_RES_KEPT || code == VQHIP_VEC3_RES_RAW ||
-           (!(code & 0x8000) && (code & 31) <= 16 && ((code >> 5) & 31) <= 16 && ((code >> 10) & 31) <= 16);
-}
-
-inline int64_t v3r_record_size(int code)
-{
-    return code == VQHIP_VEC3_RES_KEPT ? 0 : code == VQHIP_VEC3_RES_RAW ? 6144 : 64 * (int64_t)((code & 31) + ((code >> 5) & 31) + ((code >> 10) & 31));
-}
 
 // class, scan, pack of n leaves: d_off[n] ends as the payload's size
 int v3r_encode(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, const float* d_err, int64_t n, float tol, uint16_t* d_code,
                int64_t* d_off, uint8_t* d_payload, int64_t capacity, hipStream_t s)
 {
-    hipLaunchKernelGGL(v3r::class_k, dim3(v3r_grid(n)), dim3(64 * v3r::RES_WAVES), 0, s, d_leaves, d_recon, d_err, n, tol, d_code, d_off);
+    hipLaunchKernelGGL(vqr::resid_class_k<3>, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, d_err, n, tol, d_code, d_off);
     hipLaunchKernelGGL(vqr::resid_scan_k, dim3(1), dim3(1024), 0, s, d_off, n);
-    hipLaunchKernelGGL(v3r::pack_k, dim3(v3r_grid(n)), dim3(64 * v3r::RES_WAVES), 0, s, d_leaves, d_recon, n, tol, d_code, d_off, d_payload, capacity);
+    hipLaunchKernelGGL(vqr::resid_pack_k<3>, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, d_recon, n, tol, d_code, d_off, d_payload, capacity);
     return v3_launch_check(c, "vec3 residual_encode");
 }
 
 int v3r_apply(vqhip_vec3_codec* c, float* d_leaves, int64_t n, float tol, const uint16_t* d_code, const int64_t* d_off, const uint8_t* d_payload,
               hipStream_t s)
 {
-    hipLaunchKernelGGL(v3r::apply_k, dim3(v3r_grid(n)), dim3(64 * v3r::RES_WAVES), 0, s, d_leaves, n, tol, d_code, d_off, d_payload);
+    hipLaunchKernelGGL(vqr::resid_apply_k<3>, dim3(rs_grid(n)), dim3(64 * vqr::RES_WAVES), 0, s, d_leaves, n, tol, d_code, d_off, d_payload);
     return v3_launch_check(c, "vec3 residual_apply");
 }
 
@@ -66,6 +50,20 @@ int v3r_ensure_host(vqhip_vec3_codec* c, int64_t m)
         return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 residual: cannot allocate the record buffers of " + std::to_string(m) + " leaves");
     }
     c->rs_n = m;
+    return VQHIP_OK;
+}
+
+// the tail of a chunk that v3r_encode has classed and packed: its codes, then its payload (once the size is known) go to the
+// caller's arrays and *total grows by the payload's bytes
+int v3r_fetch_chunk(vqhip_vec3_codec* c, const char* what, int64_t o, int64_t m, uint16_t* leaf_code, uint8_t* payload, int64_t* total)
+{
+    HIPCHK(c, hipMemcpyAsync(leaf_code + o, c->rs_code, (size_t)m * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    int64_t bytes = 0;
+    HIPCHK(c, hipMemcpyAsync(&bytes, c->rs_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bytes < 0 || bytes > m * 6144) return v3_fail(c, VQHIP_ERR_DEVICE, std::string(what) + ": payload size out of range");
+    if (bytes > 0) HIPCHK(c, hipMemcpy(payload + *total, c->rs_payload, (size_t)bytes, hipMemcpyDeviceToHost));
+    *total += bytes;
     return VQHIP_OK;
 }
 
@@ -125,13 +123,7 @@ int vqhip_vec3_residual_compress(vqhip_vec3_codec* c, const float* leaves, int64
         if (leaf_err)
             HIPCHK(c, hipMemcpyAsync(leaf_err + o * VQHIP_VEC3_ERR_FLOATS, c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float),
                                      hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(leaf_code + o, c->rs_code, (size_t)m * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-        int64_t bytes = 0;
-        HIPCHK(c, hipMemcpyAsync(&bytes, c->rs_off + m, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (bytes < 0 || bytes > m * 6144) return v3_fail(c, VQHIP_ERR_DEVICE, "vec3 compress_residual: payload size out of range");
-        if (bytes > 0) HIPCHK(c, hipMemcpy(payload + total, c->rs_payload, (size_t)bytes, hipMemcpyDeviceToHost));
-        total += bytes;
+        if ((rc = v3r_fetch_chunk(c, "vec3 compress_residual", o, m, leaf_code, payload, &total))) return rc;
     }
     *payload_bytes = total;
     return VQHIP_OK;
@@ -147,13 +139,13 @@ int vqhip_vec3_residual_decompress(vqhip_vec3_codec* c, const uint16_t* indices,
         return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decompress_residual: null pointer");
     int64_t need = 0;
     for (int64_t i = 0; i < n; ++i) {
-        if (!v3r_code_ok(leaf_code[i])) {
+        if (!vqr::code_ok<3>(leaf_code[i])) {
             char hex[8];
             std::snprintf(hex, sizeof hex, "0x%04X", (unsigned)leaf_code[i]);
             return v3_fail(c, VQHIP_ERR_INVALID, std::string("vec3 decompress_residual: code ") + hex + " of leaf " + std::to_string(i) +
                                                      " is neither 0xFFFE, 0xFFFF nor three widths of 0..16");
         }
-        need += v3r_record_size(leaf_code[i]);
+        need += vqr::record_size<3>(leaf_code[i]);
     }
     if (need != payload_bytes)
         return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decompress_residual: the codes need " + std::to_string(need) + " payload bytes, the caller gives " +
@@ -167,7 +159,7 @@ int vqhip_vec3_residual_decompress(vqhip_vec3_codec* c, const uint16_t* indices,
         if (int rc = v3r_ensure_host(c, m)) return rc;
         off.resize((size_t)m + 1);
         off[0] = 0;
-        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + v3r_record_size(leaf_code[o + i]);
+        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + vqr::record_size<3>(leaf_code[o + i]);
         HIPCHK(c, hipMemcpy(c->io_idx, indices + o * 64, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->rs_code, leaf_code + o, (size_t)m * sizeof(uint16_t), hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->rs_off, off.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
