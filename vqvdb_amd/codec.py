@@ -143,6 +143,10 @@ RATE_SYMBOLS = ["vqhip_rate_payload_bytes", "vqhip_rate_sidecar_bytes", "vqhip_r
                 "vqhip_rate_compress_file"]
 RATE_MAX_TOLS, RATE_CLASSES = 64, 19   # VQHIP_RATE_MAX_TOLS, VQHIP_RATE_CLASSES: columns 0 .. 16 quantised, 17 raw, 18 kept
 ERR_FLOATS = 2   # VQHIP_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
+# every symbol include/vqvdb_hip_vec3_mask.h declares (active-voxel masks of the Vec3 handle's residual codec; kept apart from the lists above)
+VEC3_MASK_SYMBOLS = ["vqhip_vec3_mask_leaf_err_device", "vqhip_vec3_mask_residual_encode_device", "vqhip_vec3_mask_sweep_device",
+                     "vqhip_vec3_mask_compress_residual", "vqhip_vec3_mask_sweep"]
+MASK_WORDS = 8   # VQHIP_VEC3_MASK_WORDS: uint64 words of one leaf's mask, bit L of word j = voxel 64 j + L
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
 
@@ -351,6 +355,14 @@ def load_library() -> ctypes.CDLL:
                                              ctypes.POINTER(StreamStats), ctypes.POINTER(BoundedStats), ctypes.POINTER(ResidualStats)]
     for name in RATE_SYMBOLS:
         getattr(lib, name).restype = i64 if name.endswith("_bytes") else ci
+    # include/vqvdb_hip_vec3_mask.h
+    lib.vqhip_vec3_mask_leaf_err_device.argtypes = [vp, vp, vp, vp, i64, vp, vp]
+    lib.vqhip_vec3_mask_residual_encode_device.argtypes = [vp, vp, vp, vp, vp, i64, cf, vp, vp, vp, i64, vp]
+    lib.vqhip_vec3_mask_sweep_device.argtypes = [vp, vp, vp, vp, vp, i64, vp, ci, vp, vp]
+    lib.vqhip_vec3_mask_compress_residual.argtypes = [vp, vp, vp, i64, cf, vp, vp, vp, vp, vp]
+    lib.vqhip_vec3_mask_sweep.argtypes = [vp, vp, vp, i64, vp, ci, vp]
+    for name in VEC3_MASK_SYMBOLS:
+        getattr(lib, name).restype = ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -370,6 +382,31 @@ def load_library() -> ctypes.CDLL:
             getattr(lib, name).restype = ci
     _lib = lib
     return lib
+
+
+def pack_masks(active) -> np.ndarray:
+    """bool [n,512] or [n,8,8,8] (voxel offset d*64 + h*8 + w) -> uint64 [n,8]: bit L of word j of a leaf is voxel 64 j + L, the
+    words of OpenVDB's NodeMask<3> (leaf.valueMask()) that the masked calls take."""
+    a = np.asarray(active)
+    if a.dtype != np.bool_:
+        raise TypeError("active must be a bool array")
+    if not ((a.ndim == 2 and a.shape[1] == 512) or (a.ndim == 4 and a.shape[1:] == (8, 8, 8))):
+        raise ValueError(f"active must have shape [n,512] or [n,8,8,8], got {list(a.shape)}")
+    bits = np.packbits(a.reshape(-1, MASK_WORDS, 8, 8), axis=-1, bitorder="little")    # [n, word, byte, 1]: byte b holds the voxels 8 b .. 8 b + 7
+    return np.ascontiguousarray(bits.reshape(-1, MASK_WORDS, 8)).view("<u8").reshape(-1, MASK_WORDS).astype(np.uint64)
+
+
+def check_masks(masks, n: int) -> np.ndarray:
+    """uint64, C-contiguous, [n,8] (what pack_masks returns; OpenVDB's mask words unconverted) -> the same array."""
+    if not isinstance(masks, np.ndarray) or masks.dtype != np.uint64:
+        raise TypeError("masks must be a uint64 numpy array (pack_masks turns a bool array into one)")
+    if masks.ndim != 2 or masks.shape[1] != MASK_WORDS:
+        raise ValueError(f"masks must have shape [n,8], got {list(masks.shape)}")
+    if masks.shape[0] != n:
+        raise ValueError(f"{n} leaves but {masks.shape[0]} masks")
+    if not masks.flags.c_contiguous:
+        raise ValueError("masks must be C-contiguous")
+    return masks
 
 
 VEC3_LEAF_SHAPE = (512, 3)
@@ -769,6 +806,56 @@ class HipVec3Codec:
                                                        payload.ctypes.data, ctypes.byref(nbytes)))
         out = (used.value, hist, idx, lc, payload[:nbytes.value].copy())
         return out + (err,) if return_leaf_err else out
+
+    # ---- active-voxel masks: include/vqvdb_hip_vec3_mask.h ----
+    def mask_leaf_err_device(self, leaves_ptr: int, recon_ptr: int, mask_ptr: int, n: int, leaf_err_ptr: int, stream: int = 0):
+        """vqhip_vec3_mask_leaf_err_device: leaf_err [n,2] over the active values of masks uint64 [n,8] (one bit per voxel, three channels)."""
+        if n > 0 and not (leaves_ptr and recon_ptr and mask_ptr and leaf_err_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, mask and leaf_err are required")
+        self._check(self._lib.vqhip_vec3_mask_leaf_err_device(self._h, leaves_ptr, recon_ptr, mask_ptr, n, leaf_err_ptr, stream or None))
+
+    def mask_residual_encode_device(self, leaves_ptr: int, recon_ptr: int, mask_ptr: int, leaf_err_ptr: int, n: int, tol: float, code_ptr: int,
+                                    offsets_ptr: int, payload_ptr: int, payload_capacity: int, stream: int = 0):
+        """vqhip_vec3_mask_residual_encode_device: residual_encode_device on the masked error and the active values."""
+        if n > 0 and not (leaves_ptr and recon_ptr and mask_ptr and leaf_err_ptr and code_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, mask, leaf_err, code and offsets are required")
+        if payload_capacity < 0:
+            raise ValueError("payload_capacity must be >= 0")
+        tol = self.check_tol(tol)
+        self._check(self._lib.vqhip_vec3_mask_residual_encode_device(self._h, leaves_ptr, recon_ptr, mask_ptr, leaf_err_ptr, n, tol, code_ptr,
+                                                                     offsets_ptr, payload_ptr or None, payload_capacity, stream or None))
+
+    def mask_sweep_device(self, leaves_ptr: int, recon_ptr: int, mask_ptr: int, leaf_err_ptr: int, n: int, tols, hist_ptr: int, stream: int = 0):
+        """vqhip_vec3_mask_sweep_device: rate_sweep_device on the masked error and the active values; ADDS to hist_ptr."""
+        tols = self.check_tols(tols)
+        if n > 0 and not (leaves_ptr and recon_ptr and mask_ptr and leaf_err_ptr and hist_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, mask, leaf_err and hist are required")
+        self._check(self._lib.vqhip_vec3_mask_sweep_device(self._h, leaves_ptr, recon_ptr, mask_ptr, leaf_err_ptr, n, tols.ctypes.data, len(tols),
+                                                           hist_ptr, stream or None))
+
+    def compress_residual_masked(self, leaves: np.ndarray, masks: np.ndarray, tol: float, return_leaf_err: bool = False):
+        """compress_residual with value masks uint64 [n,8] (pack_masks): the tolerance holds on the active voxels and inactive
+        ones cost nothing.  -> (indices, leaf_code, payload[, masked leaf_err]), read by decompress_residual unchanged."""
+        leaves = self.check_leaves(leaves)
+        n = leaves.shape[0]
+        masks = check_masks(masks, n)
+        tol = self.check_tol(tol)
+        idx, err = np.empty((n, 64), dtype=np.uint16), np.empty((n, VEC3_ERR_FLOATS), dtype=np.float32)
+        lc, payload, nbytes = np.empty(n, dtype=np.uint16), np.empty(n * 6144, dtype=np.uint8), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_mask_compress_residual(self._h, leaves.ctypes.data, masks.ctypes.data, n, tol, idx.ctypes.data, err.ctypes.data,
+                                                                lc.ctypes.data, payload.ctypes.data, ctypes.byref(nbytes)))
+        out = (idx, lc, payload[:nbytes.value].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def rate_sweep_masked(self, leaves: np.ndarray, masks: np.ndarray, tols) -> np.ndarray:
+        """rate_sweep with value masks: hist int64 [T,51] of compress_residual_masked at every rung."""
+        leaves = self.check_leaves(leaves)
+        masks = check_masks(masks, leaves.shape[0])
+        tols = self.check_tols(tols)
+        hist = np.empty((len(tols), VEC3_RATE_CLASSES), dtype=np.int64)
+        self._check(self._lib.vqhip_vec3_mask_sweep(self._h, leaves.ctypes.data, masks.ctypes.data, leaves.shape[0], tols.ctypes.data, len(tols),
+                                                    hist.ctypes.data))
+        return hist
 
     # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----
     @staticmethod

@@ -15,6 +15,14 @@
 // int32; at the end the workgroup adds its non-zero cells to the global histogram with 64-bit integer atomics.  Integer sums: the
 // histogram is the same bits at every grid size, on every stream and for every split of the leaves over calls.  No float atomics,
 // no scratch, no spills.
+//
+// MASKED (vq_mask.h, include/vqvdb_hip_vec3_mask.h; instantiated for C = 3): err is the masked error and mask [n][8] the leaves' value masks.  The
+// wave's leaf index is uniform, so the eight words of a leaf arrive by scalar loads and lane l tests bit l of each.  The rung loop
+// keeps no mask: the lane's values of an inactive voxel are loaded as x = x^ = +0, whatever the arrays hold there.  Such a pair
+// gives q = 0 (nothing in the union) and verifies at every rung with a finite step > 0; it fails only where the step is 0, NaN or
+// infinite or the rung negative, and there every active value fails as well (t is NaN or infinite, x^ + 0 * inf is NaN, or
+// |x - x~| <= tol < 0 is false), so the leaf is raw by its active values alone.  That leaves the leaf without an active voxel, a
+// wave-uniform case: where it is selected it counts in column 0.  The early exit uses the masked error.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -42,9 +50,10 @@ struct Tols {   // by value in the kernel's arguments: the rungs are read with s
     float t[RATE_MAX_TOLS];
 };
 
-template <int C>
+template <int C, bool MASKED = false>
 __global__ void __launch_bounds__(64 * RATE_WAVES) sweep_k(const float* __restrict__ orig, const float* __restrict__ recon, const float* __restrict__ err,
-                                                          int64_t n, const Tols tols, unsigned long long* __restrict__ hist)
+                                                          int64_t n, const Tols tols, unsigned long long* __restrict__ hist,
+                                                          const unsigned long long* __restrict__ mask = nullptr)
 {
     __shared__ int tab[RATE_MAX_TOLS * CLASSES<C>];
     const int lane = threadIdx.x & 63;
@@ -60,7 +69,7 @@ __global__ void __launch_bounds__(64 * RATE_WAVES) sweep_k(const float* __restri
         least = tol < least ? tol : least;
     }
     __syncthreads();
-    for (int64_t leaf = (int64_t)blockIdx.x * RATE_WAVES + (threadIdx.x >> 6); leaf < n; leaf += (int64_t)gridDim.x * RATE_WAVES) {
+    for (int64_t leaf = (int64_t)blockIdx.x * RATE_WAVES + vqr::wave_of_block<MASKED>(); leaf < n; leaf += (int64_t)gridDim.x * RATE_WAVES) {
         const float e = __int_as_float(vqr::uniform(__float_as_int(err[leaf * 2])));
         if (!nan_rung && e <= least) {   // kept at every rung: nothing else of the leaf is read
             if (lane < count) atomicAdd(&tab[lane * CLASSES<C> + COL_KEPT<C>], 1);
@@ -75,12 +84,32 @@ __global__ void __launch_bounds__(64 * RATE_WAVES) sweep_k(const float* __restri
 #pragma unroll
             for (int ch = 0; ch < C; ++ch) xv[j][ch] = x[at + ch], rv[j][ch] = r[at + ch];
         }
+        [[maybe_unused]] bool empty = false;   // MASKED: the leaf has no active voxel
+        if constexpr (MASKED) {
+            unsigned long long some = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const unsigned long long w = mask[leaf * 8 + j];
+                some |= w;
+                if (!((w >> lane) & 1ull)) {
+#pragma unroll
+                    for (int ch = 0; ch < C; ++ch) xv[j][ch] = 0.0f, rv[j][ch] = 0.0f;
+                }
+            }
+            empty = some == 0ull;
+        }
 #pragma unroll 1
         for (int t = 0; t < count; ++t) {
             const float tol = tols.t[t];
             if (e <= tol) {      // the selection rule of resid_class_k: equality keeps, NaN on either side selects
                 if (lane == 0) atomicAdd(&tab[t * CLASSES<C> + COL_KEPT<C>], 1);
                 continue;
+            }
+            if constexpr (MASKED) {
+                if (empty) {     // selected without an active voxel: code 0, no record
+                    if (lane == 0) atomicAdd(&tab[t * CLASSES<C>], 1);
+                    continue;
+                }
             }
             const float step = __fmul_rn(1.875f, tol);
             unsigned bad = 0, any[C];

@@ -21,6 +21,11 @@
 // (consecutive floats), so a plane word is one ballot and a lane finds its bit again with one shift.  One wave per leaf,
 // RES_WAVES leaves per workgroup, whole waves leave early; no LDS, no barrier, no atomics (the scan aside, which is one workgroup
 // with a running carry): what is written for a leaf depends on that leaf and its offset alone.
+//
+// MASKED (vq_mask.h, include/vqvdb_hip_vec3_mask.h; instantiated for C = 3): leaf_zigzag, resid_class_k and resid_pack_k also take the leaves'
+// value masks, uint64 [n][8], bit L of word j = voxel 64 j + L, which is the lane-to-voxel map above: the wave's leaf index is made
+// uniform, word j arrives by a scalar load and lane l tests bit l.  A value of an inactive voxel has zz = 0 and verifies whatever
+// x and x^ hold there; everything else is the rule above on the active values.  The records and resid_apply_k do not change.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -91,10 +96,20 @@ __device__ __forceinline__ unsigned zigzag(int q)
     return ((unsigned)q << 1) ^ (unsigned)(q >> 31);
 }
 
-// the lane's 8 * C values (voxels 64 j + lane, C channels each) of x and x^ -> zz(q) of each; false if one of them does not verify
-template <int C>
+// the wave of a workgroup of 64-lane waves, and with MASKED as a scalar: the leaf index and with it the address of the leaf's mask
+// words are then uniform by construction
+template <bool MASKED>
+__device__ __forceinline__ int wave_of_block()
+{
+    if constexpr (MASKED) return uniform((int)(threadIdx.x >> 6));
+    else return (int)(threadIdx.x >> 6);
+}
+
+// the lane's 8 * C values (voxels 64 j + lane, C channels each) of x and x^ -> zz(q) of each; false if one of them does not verify.
+// MASKED: mask is the leaf's eight words (a uniform address); an inactive voxel's values give zz = 0 and never fail
+template <int C, bool MASKED = false>
 __device__ __forceinline__ bool leaf_zigzag(const float* __restrict__ x, const float* __restrict__ r, int lane, float step, float tol,
-                                            unsigned (&zz)[8][C])
+                                            unsigned (&zz)[8][C], const unsigned long long* __restrict__ mask = nullptr)
 {
     bool ok = true;
 #pragma unroll
@@ -103,32 +118,43 @@ __device__ __forceinline__ bool leaf_zigzag(const float* __restrict__ x, const f
         float xv[C], rv[C];
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) xv[ch] = x[at + ch], rv[ch] = r[at + ch];
+        bool active = true;
+        if constexpr (MASKED) active = (mask[j] >> lane) & 1ull;
 #pragma unroll
         for (int ch = 0; ch < C; ++ch) {
             int q;
-            ok = quantise(xv[ch], rv[ch], step, tol, q) && ok;
-            zz[j][ch] = zigzag(q);
+            const bool fine = quantise(xv[ch], rv[ch], step, tol, q);
+            if constexpr (MASKED) {
+                ok = (fine || !active) && ok;
+                zz[j][ch] = active ? zigzag(q) : 0u;
+            } else {
+                ok = fine && ok;
+                zz[j][ch] = zigzag(q);
+            }
         }
     }
     return ok;
 }
 
-// code[leaf] and size[leaf] (the record's bytes; resid_scan_k turns them into offsets in place) of every leaf
-template <int C>
+// code[leaf] and size[leaf] (the record's bytes; resid_scan_k turns them into offsets in place) of every leaf.  MASKED: err is the
+// masked error and mask [n][8] the value masks; a selected leaf without an active voxel gets code 0
+template <int C, bool MASKED = false>
 __global__ void __launch_bounds__(64 * RES_WAVES) resid_class_k(const float* __restrict__ orig, const float* __restrict__ recon,
                                                                const float* __restrict__ err, int64_t n, float tol,
-                                                               typename Format<C>::code_t* __restrict__ code, int64_t* __restrict__ size)
+                                                               typename Format<C>::code_t* __restrict__ code, int64_t* __restrict__ size,
+                                                               const unsigned long long* __restrict__ mask = nullptr)
 {
     using code_t = typename Format<C>::code_t;
     const int lane = threadIdx.x & 63;
-    const int64_t leaf = (int64_t)blockIdx.x * RES_WAVES + (threadIdx.x >> 6);
+    const int64_t leaf = (int64_t)blockIdx.x * RES_WAVES + wave_of_block<MASKED>();
     if (leaf >= n) return;
     if (err[leaf * 2] <= tol) {   // kept: nothing else of the leaf is read
         if (lane == 0) code[leaf] = (code_t)Format<C>::KEPT, size[leaf] = 0;
         return;
     }
     unsigned zz[8][C];
-    const bool ok = leaf_zigzag<C>(orig + leaf * (512 * C), recon + leaf * (512 * C), lane, __fmul_rn(1.875f, tol), tol, zz);
+    const bool ok = leaf_zigzag<C, MASKED>(orig + leaf * (512 * C), recon + leaf * (512 * C), lane, __fmul_rn(1.875f, tol), tol, zz,
+                                           MASKED ? mask + leaf * 8 : nullptr);
     unsigned any[C];
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {
@@ -189,14 +215,16 @@ __global__ void __launch_bounds__(1024) resid_scan_k(int64_t* __restrict__ size,
     if (tid == 0) size[n] = carry_s;
 }
 
-// every selected leaf's record at payload + off[leaf]; a record that ends beyond `capacity` is not written at all
-template <int C>
+// every selected leaf's record at payload + off[leaf]; a record that ends beyond `capacity` is not written at all.  MASKED: the
+// bits of an inactive voxel are 0 in a quantised record; a raw record is the leaf as given, inactive voxels included
+template <int C, bool MASKED = false>
 __global__ void __launch_bounds__(64 * RES_WAVES) resid_pack_k(const float* __restrict__ orig, const float* __restrict__ recon, int64_t n, float tol,
                                                               const typename Format<C>::code_t* __restrict__ code, const int64_t* __restrict__ off,
-                                                              uint8_t* __restrict__ payload, int64_t capacity)
+                                                              uint8_t* __restrict__ payload, int64_t capacity,
+                                                              const unsigned long long* __restrict__ mask = nullptr)
 {
     const int lane = threadIdx.x & 63;
-    const int64_t leaf = (int64_t)blockIdx.x * RES_WAVES + (threadIdx.x >> 6);
+    const int64_t leaf = (int64_t)blockIdx.x * RES_WAVES + wave_of_block<MASKED>();
     if (leaf >= n) return;
     const int c = uniform(code[leaf]);
     if (c == Format<C>::KEPT || c == 0) return;
@@ -210,7 +238,7 @@ __global__ void __launch_bounds__(64 * RES_WAVES) resid_pack_k(const float* __re
         return;
     }
     unsigned zz[8][C];
-    leaf_zigzag<C>(x, recon + leaf * (512 * C), lane, __fmul_rn(1.875f, tol), tol, zz);
+    leaf_zigzag<C, MASKED>(x, recon + leaf * (512 * C), lane, __fmul_rn(1.875f, tol), tol, zz, MASKED ? mask + leaf * 8 : nullptr);
     unsigned long long* dst = reinterpret_cast<unsigned long long*>(payload + at);
 #pragma unroll
     for (int ch = 0; ch < C; ++ch) {

@@ -47,6 +47,9 @@ struct vqhip_vec3_codec {
     int64_t rs_n = 0;
     // size sweep (vq_vec3_rate.inc), host calls: the histogram [64][51], allocated on first use
     int64_t* rate_hist = nullptr;
+    // active-voxel masks (vq_vec3_mask.inc), host calls: one chunk's masks [mk_n][8]
+    uint64_t* mk_mask = nullptr;
+    int64_t mk_n = 0;
     struct Dbg {
         float* p = nullptr;
         int64_t cap = 0, n = 0;
@@ -588,6 +591,7 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     if (c->rs_off) hipFree(c->rs_off);
     if (c->rs_payload) hipFree(c->rs_payload);
     if (c->rate_hist) hipFree(c->rate_hist);
+    if (c->mk_mask) hipFree(c->mk_mask);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
