@@ -15,24 +15,10 @@ int bd_launch_check(vqhip_codec* c, const char* what)
     return VQHIP_OK;
 }
 
-// grow-only device buffer of `count` elements; an earlier, smaller one may still be read by work on any stream
-template <typename T>
-int bd_grow(vqhip_codec* c, T*& buf, int64_t& have, int64_t count, const char* what)
+// the error text of a failed ensure() of `count` elements
+auto bd_nomem(const char* what, int64_t count)
 {
-    if (count <= have) return VQHIP_OK;
-    if (buf) {
-        HIPCHK(c, hipDeviceSynchronize());
-        hipFree(buf);
-        buf = nullptr;
-        have = 0;
-    }
-    if (hipMalloc(&buf, (size_t)count * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        buf = nullptr;
-        return fail(c, VQHIP_ERR_NOMEM, std::string("bounded: cannot allocate ") + what + " (" + std::to_string(count) + " elements)");
-    }
-    have = count;
-    return VQHIP_OK;
+    return [=](hipError_t) { return std::string("bounded: cannot allocate ") + what + " (" + std::to_string(count) + " elements)"; };
 }
 
 // the chunk's leaf errors from the caller's leaves and its reconstruction
@@ -48,11 +34,13 @@ int bd_leaf_err(vqhip_codec* c, const float* d_leaves, const float* d_recon, int
 int bd_roundtrip_chunk(vqhip_codec* c, const float* d_leaves, int64_t m, uint8_t* d_idx, float* d_recon, float* d_err, hipStream_t s)
 {
     if (!d_idx) {
-        if (int rc = bd_grow(c, c->bd_idx, c->bd_idx_leaves, std::max(m, std::min<int64_t>(c->chunk, 65536)) * 64, "the index chunk")) return rc;
+        const int64_t count = std::max(m, std::min<int64_t>(c->chunk, 65536)) * 64;
+        if (int rc = ensure(c, c->bd_idx, count, bd_nomem("the index chunk", count))) return rc;
         d_idx = c->bd_idx;
     }
     if (!d_recon) {
-        if (int rc = bd_grow(c, c->bd_recon, c->bd_recon_leaves, std::max(m, std::min<int64_t>(c->chunk, 65536)) * 512, "the reconstruction chunk")) return rc;
+        const int64_t count = std::max(m, std::min<int64_t>(c->chunk, 65536)) * 512;
+        if (int rc = ensure(c, c->bd_recon, count, bd_nomem("the reconstruction chunk", count))) return rc;
         d_recon = c->bd_recon;
     }
     if (int rc = encode_chunk(c, d_leaves, m, d_idx, s)) return rc;
@@ -63,7 +51,7 @@ int bd_roundtrip_chunk(vqhip_codec* c, const float* d_leaves, int64_t m, uint8_t
 int bd_select(vqhip_codec* c, const float* d_err, int64_t n, float tol, int64_t* d_ids, int64_t* d_count, hipStream_t s)
 {
     const int64_t nb = (n + v3e::SEL_BLOCK - 1) / v3e::SEL_BLOCK;
-    if (int rc = bd_grow(c, c->bd_scan, c->bd_scan_n, std::max<int64_t>(nb, 64), "the selection's scan buffer")) return rc;
+    if (int rc = ensure(c, c->bd_scan, std::max<int64_t>(nb, 64), bd_nomem("the selection's scan buffer", std::max<int64_t>(nb, 64)))) return rc;
     hipLaunchKernelGGL(v3e::select_k<false>, dim3((unsigned)nb), dim3(v3e::SEL_BLOCK), 0, s, d_err, n, tol, c->bd_scan, d_ids);
     hipLaunchKernelGGL(v3e::select_scan_k, dim3(1), dim3(1024), 0, s, c->bd_scan, nb, d_count);
     hipLaunchKernelGGL(v3e::select_k<true>, dim3((unsigned)nb), dim3(v3e::SEL_BLOCK), 0, s, d_err, n, tol, c->bd_scan, d_ids);
@@ -73,19 +61,10 @@ int bd_select(vqhip_codec* c, const float* d_err, int64_t n, float tol, int64_t*
 // leaf errors of the host calls: a device buffer and a pinned landing zone per I/O slot, m leaves each
 int bd_ensure_pipe(vqhip_codec* c, int64_t m)
 {
-    if (m <= c->bd_err_leaves) return VQHIP_OK;
-    HIPCHK(c, hipDeviceSynchronize());
     for (int i = 0; i < 2; ++i) {
-        if (c->bd_err[i]) hipFree(c->bd_err[i]);
-        if (c->bd_pin_err[i]) hipHostFree(c->bd_pin_err[i]);
-        c->bd_err[i] = nullptr, c->bd_pin_err[i] = nullptr;
+        if (int rc = ensure(c, c->bd_err[i], (size_t)m * VQHIP_ERR_FLOATS, "the leaf-error slot")) return rc;
+        if (int rc = ensure(c, c->bd_pin_err[i], (size_t)m * VQHIP_ERR_FLOATS, "the pinned leaf-error slot")) return rc;
     }
-    c->bd_err_leaves = 0;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipMalloc(&c->bd_err[i], (size_t)m * VQHIP_ERR_FLOATS * sizeof(float)));
-        HIPCHK(c, hipHostMalloc(&c->bd_pin_err[i], (size_t)m * VQHIP_ERR_FLOATS * sizeof(float), hipHostMallocDefault));
-    }
-    c->bd_err_leaves = m;
     return VQHIP_OK;
 }
 
@@ -95,7 +74,7 @@ PipeStage bd_stage(vqhip_codec* c)
 {
     return {[c](int64_t step) { return bd_ensure_pipe(c, step); },
             [c](int64_t, int64_t m, int slot, hipStream_t s) {
-                if (int rc = bd_grow(c, c->bd_recon, c->bd_recon_leaves, m * 512, "the reconstruction chunk")) return rc;
+                if (int rc = ensure(c, c->bd_recon, m * 512, bd_nomem("the reconstruction chunk", m * 512))) return rc;
                 if (int rc = decode_chunk(c, c->dev_idx[slot], m, c->bd_recon, s)) return rc;
                 return bd_leaf_err(c, c->dev_leaves[slot], c->bd_recon, m, c->bd_err[slot], s);
             },
@@ -161,7 +140,7 @@ int vqhip_compress_bounded(vqhip_codec* c, const float* leaves, int64_t n, float
         const int64_t m = std::min(c->chunk, n - o);
         if (int rc = ensure_io(c, m)) return rc;
         if (int rc = bd_ensure_pipe(c, m)) return rc;
-        if (int rc = bd_grow(c, c->bd_ids, c->bd_ids_n, m + 1, "the outlier ids")) return rc;
+        if (int rc = ensure(c, c->bd_ids, m + 1, bd_nomem("the outlier ids", m + 1))) return rc;
         int64_t* d_count = c->bd_ids + m;
         HIPCHK(c, hipMemcpyAsync(c->dev_leaves[0], leaves + o * 512, (size_t)m * 2048, hipMemcpyHostToDevice, c->stream));
         int rc = bd_roundtrip_chunk(c, c->dev_leaves[0], m, c->dev_idx[0], nullptr, c->bd_err[0], c->stream);

@@ -94,7 +94,7 @@ int rate_sweep(vqhip_codec* c, const float* d_leaves, const float* d_recon, cons
 // the handle's histogram, cleared on the compute stream
 int rate_begin(vqhip_codec* c)
 {
-    if (!c->rate_hist) HIPCHK(c, hipMalloc(&c->rate_hist, RATE_HIST_BYTES));
+    if (int rc = ensure(c, c->rate_hist, RATE_HIST_BYTES / sizeof(int64_t), "the size-sweep histogram")) return rc;
     HIPCHK(c, hipMemsetAsync(c->rate_hist, 0, RATE_HIST_BYTES, c->stream));
     return VQHIP_OK;
 }

@@ -45,37 +45,23 @@ int rs_apply(vqhip_codec* c, float* d_leaves, int64_t n, float tol, const uint8_
 // {int64 total | m + 1 offsets | m * 2048 payload bytes | m classes} (the file pair's landing zone and upload staging)
 int rs_ensure(vqhip_codec* c, int64_t m, bool pinned)
 {
-    if (m > c->rs_leaves) {
-        HIPCHK(c, hipDeviceSynchronize());
-        for (int i = 0; i < 2; ++i) {
-            if (c->rs_class[i]) hipFree(c->rs_class[i]);
-            if (c->rs_off[i]) hipFree(c->rs_off[i]);
-            if (c->rs_payload[i]) hipFree(c->rs_payload[i]);
-            if (c->rs_pin[i]) hipHostFree(c->rs_pin[i]);
-            c->rs_class[i] = nullptr, c->rs_off[i] = nullptr, c->rs_payload[i] = nullptr, c->rs_pin[i] = nullptr;
-        }
-        c->rs_leaves = 0, c->rs_pin_leaves = 0;
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(c, hipMalloc(&c->rs_class[i], (size_t)m));
-            HIPCHK(c, hipMalloc(&c->rs_off[i], (size_t)(m + 1) * sizeof(int64_t)));
-            HIPCHK(c, hipMalloc(&c->rs_payload[i], (size_t)m * 2048));
-        }
-        c->rs_leaves = m;
+    for (int i = 0; i < 2; ++i) {
+        if (int rc = ensure(c, c->rs_class[i], (size_t)m, "the residual classes")) return rc;
+        if (int rc = ensure(c, c->rs_off[i], (size_t)m + 1, "the residual offsets")) return rc;
+        if (int rc = ensure(c, c->rs_payload[i], (size_t)m * 2048, "the residual payload")) return rc;
     }
-    if (pinned && c->rs_pin_leaves < c->rs_leaves) {
-        HIPCHK(c, hipDeviceSynchronize());
-        for (int i = 0; i < 2; ++i) {
-            if (c->rs_pin[i]) hipHostFree(c->rs_pin[i]);
-            c->rs_pin[i] = nullptr;
-        }
-        c->rs_pin_leaves = 0;
-        for (int i = 0; i < 2; ++i) HIPCHK(c, hipHostMalloc(&c->rs_pin[i], (size_t)c->rs_leaves * (8 + 2048 + 1) + 16, hipHostMallocDefault));
-        c->rs_pin_leaves = c->rs_leaves;
+    if (pinned && c->rs_pin_leaves < m) {
+        for (int i = 0; i < 2; ++i)
+            if (int rc = ensure(c, c->rs_pin[i], (size_t)m * (8 + 2048 + 1) + 16, "the pinned residual block")) {
+                if (!c->rs_pin[i]) c->rs_pin_leaves = 0;   // (a failed synchronise leaves the old blocks and their layout)
+                return rc;
+            }
+        c->rs_pin_leaves = m;
     }
     return VQHIP_OK;
 }
 
-int64_t* rs_pin_off(vqhip_codec* c, int slot) { return reinterpret_cast<int64_t*>(c->rs_pin[slot]) + 1; }
+int64_t* rs_pin_off(vqhip_codec* c, int slot) { return reinterpret_cast<int64_t*>(c->rs_pin[slot].get()) + 1; }
 unsigned char* rs_pin_payload(vqhip_codec* c, int slot) { return c->rs_pin[slot] + (size_t)(c->rs_pin_leaves + 2) * 8; }
 unsigned char* rs_pin_class(vqhip_codec* c, int slot) { return rs_pin_payload(c, slot) + (size_t)c->rs_pin_leaves * 2048; }
 

@@ -27,6 +27,7 @@
 #include "../../include/vqvdb_hip.h"
 #include "../../include/vqvdb_hip_bounded.h"
 #include "../../include/vqvdb_hip_residual.h"
+#include "vq_buffers.h"
 #include "vq_kernels.h"
 #include "vq_conv8_lds.h"
 #include "vq_stem_taps.h"
@@ -207,20 +208,17 @@ struct vqhip_codec {
     int64_t ws_tiles = 0;
     bool ws_full = false;    // workspace layout: full (every activation at its own address: debug, training) or compact (inference)
     bool chunk_fitted = false;
-    char* ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf<char> ws;
     NameMap<float*> act;  // named activation buffers inside ws
     NameMap<std::pair<int, int>> act_shape;
 
     // host-pointer entry points: two I/O slots so H2D(i+1), compute(i) and D2H(i-1) overlap
     hipStream_t s_in = nullptr, s_out = nullptr;
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    void* pin_out[2] = {nullptr, nullptr};   // pinned landing zone for results (chunk * 2048 B each)
-    void* pin_in[2] = {nullptr, nullptr};    // pinned gather buffers of the leaf-pointer entry points (lazy)
-    size_t pin_in_bytes = 0;
-    float* dev_leaves[2] = {nullptr, nullptr};  // chunk * 512 floats
-    uint8_t* dev_idx[2] = {nullptr, nullptr};   // chunk * 64 bytes
-    int64_t dev_io_leaves = 0;
+    PinBuf<unsigned char> pin_out[2];   // pinned landing zone for results (chunk * 2048 B each)
+    PinBuf<unsigned char> pin_in[2];    // pinned gather buffers of the leaf-pointer entry points
+    DevBuf<float> dev_leaves[2];        // chunk * 512 floats
+    DevBuf<uint8_t> dev_idx[2];         // chunk * 64 bytes
 
     // profiling
     bool profiling = false;
@@ -232,20 +230,18 @@ struct vqhip_codec {
     // latent / index scratch for one training batch
     std::vector<float> h_proj_w, h_proj_b;
     bool training = false, tables_stale = false;
-    float* tr_z = nullptr;
-    uint8_t* tr_idx = nullptr;
-    int64_t tr_leaves = 0;
+    DevBuf<float> tr_z;
+    DevBuf<uint8_t> tr_idx;
     // full training step (vq_train_full.inc)
     std::vector<float> h_params;                                   // raw tensors, state_dict order
     std::map<std::string, std::pair<int64_t, int64_t>> p_off;      // name -> (offset, count) in the flat parameter vector
-    float *ft_P = nullptr, *ft_M = nullptr, *ft_V = nullptr;       // parameters, AdamW moments (device, flat)
-    void* ft_refrag_jobs = nullptr;                                 // device job table of refrag_multi_k (vq_train_full.inc: refrag_all)
+    DevBuf<float> ft_P, ft_M, ft_V;                                // parameters, AdamW moments (device, flat)
+    DevBuf<unsigned char> ft_refrag_jobs;                          // device job table of refrag_multi_k (vq_train_full.inc: refrag_all)
     int ft_refrag_n = 0, ft_refrag_wgs = 0;
     const void* ft_refrag_P = nullptr;                              // the parameter block the cached job table points into
-    char* ft_ws = nullptr;                                         // training workspace (saved activations, gradients)
-    int64_t ft_tiles = 0;
-    char* ft_part = nullptr;                                       // partial-gradient scratch
-    size_t ft_part_bytes = 0;
+    DevBuf<char> ft_ws;                                            // training workspace (saved activations, gradients)
+    int64_t ft_tiles = 0;                                          // ... laid out for this many tiles
+    DevBuf<char> ft_part;                                          // partial-gradient scratch
     bool full_training = false, keep_y1 = false, weights_stale = false;
     bool train_gn_fused = true;      // GroupNorm + ReLU backward as one pass per layer (gn_bwd_fused_k); VQHIP_TRAIN_GNBWD=split: sums + finish + apply
     bool train_bias_main = true;     // bias gradients on the data-gradient stream when there is no reduction stream (VQHIP_TRAIN_BIAS=side: beside the weight gradients)
@@ -268,32 +264,24 @@ struct vqhip_codec {
     bool train_ema_lists = true;     // codebook statistics from per-(segment, code) member lists (vq_ema_lists_k + vq_ema_gather_k); VQHIP_TRAIN_EMA=scan: every (code, segment) wave scans the indices
     bool train_folded_tail = true;   // training step: up_conv + PixelShuffle3D + final as one folded operator (vq_train_tail.h); VQHIP_TRAIN_TAIL=unfolded keeps the layer-by-layer tail
     float* z4_out = nullptr;   // set around encode_chunk by the training forward: latent also in the L4 layout
-    char* tr_part = nullptr;   // per-(code, row segment) partial statistics
-    size_t tr_part_bytes = 0;
-    float* tr_recon = nullptr;  // reconstruction scratch of vqhip_train_eval_device
-    int64_t tr_recon_leaves = 0;
-    double* tr_loss_part = nullptr;
-    // error-bounded calls (vq_bounded.inc): every buffer lazy, sized to the largest chunk seen, freed in vqhip_destroy
-    float* bd_recon = nullptr;      // a chunk's reconstruction when the caller wants none stored
-    int64_t bd_recon_leaves = 0;
-    uint8_t* bd_idx = nullptr;      // a chunk's indices when the caller wants none
-    int64_t bd_idx_leaves = 0;
-    float* bd_err[2] = {nullptr, nullptr};       // leaf errors of the host calls, one per I/O slot ...
-    float* bd_pin_err[2] = {nullptr, nullptr};   // ... and their pinned landing zones
-    int64_t bd_err_leaves = 0;
-    int64_t* bd_ids = nullptr;      // outlier ids of one chunk, the count behind them
-    int64_t bd_ids_n = 0;
-    int64_t* bd_scan = nullptr;     // block counts / offsets of the selection
-    int64_t bd_scan_n = 0;
-    // quantised residuals (vq_residual.inc): lazy, sized to the largest chunk seen, freed in vqhip_destroy; one set per I/O slot
-    uint8_t* rs_class[2] = {nullptr, nullptr};
-    int64_t* rs_off[2] = {nullptr, nullptr};
-    uint8_t* rs_payload[2] = {nullptr, nullptr};
-    int64_t rs_leaves = 0;
-    unsigned char* rs_pin[2] = {nullptr, nullptr};   // the file pair's pinned block: total, offsets, payload, classes
-    int64_t rs_pin_leaves = 0;
-    // size sweep (vq_rate.inc): the histogram [64][19] of the host calls, allocated on first use, freed in vqhip_destroy
-    int64_t* rate_hist = nullptr;
+    DevBuf<char> tr_part;      // per-(code, row segment) partial statistics
+    DevBuf<float> tr_recon;    // reconstruction scratch of vqhip_train_eval_device
+    DevBuf<double> tr_loss_part;
+    // error-bounded calls (vq_bounded.inc)
+    DevBuf<float> bd_recon;        // a chunk's reconstruction when the caller wants none stored
+    DevBuf<uint8_t> bd_idx;        // a chunk's indices when the caller wants none
+    DevBuf<float> bd_err[2];       // leaf errors of the host calls, one per I/O slot ...
+    PinBuf<float> bd_pin_err[2];   // ... and their pinned landing zones
+    DevBuf<int64_t> bd_ids;        // outlier ids of one chunk, the count behind them
+    DevBuf<int64_t> bd_scan;       // block counts / offsets of the selection
+    // quantised residuals (vq_residual.inc): one set per I/O slot
+    DevBuf<uint8_t> rs_class[2];
+    DevBuf<int64_t> rs_off[2];
+    DevBuf<uint8_t> rs_payload[2];
+    PinBuf<unsigned char> rs_pin[2];   // the file pair's pinned block: total, offsets, payload, classes ...
+    int64_t rs_pin_leaves = 0;         // ... whose sections are positioned for this many leaves
+    // size sweep (vq_rate.inc): the histogram [64][19] of the host calls
+    DevBuf<int64_t> rate_hist;
 };
 
 namespace {
@@ -903,33 +891,24 @@ int ensure_workspace(vqhip_codec* c, int64_t n_leaves)
     // growing within a layout keeps the larger size; a switch to the full layout (debug, training: 2.4x the bytes per leaf) is sized
     // for what THIS call needs — a 32-leaf debug pass on a handle reserved for 65 536 leaves must not ask for 16 GB
     int64_t new_tiles = (full && !c->ws_full) ? tiles : std::max(tiles, c->ws_tiles);
-    if (c->ws) {
-        HIPCHK(c, hipDeviceSynchronize());   // the workspace may be in use on a caller's stream
-        HIPCHK(c, hipFree(c->ws));
-        c->ws = nullptr;
-        c->ws_tiles = 0;
-        c->ws_bytes = 0;
-        for (const ActSpec& a : kActs) c->act[a.name] = nullptr;   // (only this workspace's names: the training step registers its own buffers in the same table)
-    }
+    // the old block goes first, whatever its size: a switch to the full layout may ask for fewer bytes than the handle holds
+    if (c->ws) HIPCHK(c, hipDeviceSynchronize());   // the workspace may be in use on a caller's stream
+    c->ws.reset();
+    c->ws_tiles = 0;
+    for (const ActSpec& a : kActs) c->act[a.name] = nullptr;   // (only this workspace's names: the training step registers its own buffers in the same table)
     size_t total = workspace_bytes(new_tiles, full);
-    hipError_t e = hipMalloc(&c->ws, total);
-    // a failed hipMalloc leaves its error in the thread's last-error slot (ROCm 7.2 keeps it until it is read): clear it, or the next
-    // launch check reads "out of memory" for a launch that succeeded and turns a good retry / the promised smaller-chunk call into a failure
-    if (e != hipSuccess) (void)hipGetLastError();
+    hipError_t e = c->ws.grow(total);
     if (e != hipSuccess && new_tiles > tiles) {   // the larger-than-needed size did not fit: what the call needs
         new_tiles = tiles;
         total = workspace_bytes(new_tiles, full);
-        e = hipMalloc(&c->ws, total);
-        if (e != hipSuccess) (void)hipGetLastError();
+        e = c->ws.grow(total);
     }
     if (e != hipSuccess) {
-        // the handle holds no workspace now (ws_bytes 0, every activation pointer null); the chunk is re-fitted to the free memory
+        // the handle holds no workspace now (every activation pointer null); the chunk is re-fitted to the free memory
         // at the next host-pointer call, so a caller that retries after a transient shortage gets a smaller chunk instead of this error
-        c->ws = nullptr;
         c->chunk_fitted = false;
         return fail(c, VQHIP_ERR_NOMEM, std::string("workspace hipMalloc of ") + std::to_string(total >> 20) + " MiB failed: " + hipGetErrorString(e));
     }
-    c->ws_bytes = total;
     auto sz = [&](size_t per_leaf_floats) { return ((per_leaf_floats * sizeof(float) * 32 * (size_t)new_tiles) + 255) / 256 * 256; };
     size_t off = 0, region_off[kRegions] = {0, 0, 0};
     if (!full) {   // the three shared regions first
@@ -961,7 +940,7 @@ void fit_chunk_to_free_memory(vqhip_codec* c)
 {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;
-    free_b += c->ws_bytes;   // what this handle already holds can be re-used
+    free_b += c->ws.bytes();   // what this handle already holds can be re-used
     while (c->chunk > 2048) {
         const size_t need = workspace_bytes((c->chunk + 31) / 32, want_full_layout(c)) + (size_t)c->chunk * (2 * 2048 + 2 * 64);
         if (need <= free_b / 5 * 4) break;
@@ -1557,34 +1536,19 @@ int ensure_io(vqhip_codec* c, int64_t n)
             HIPCHK(c, hipEventCreateWithFlags(&c->ev_out[i], hipEventDisableTiming));
         }
     }
-    if (n <= c->dev_io_leaves) return VQHIP_OK;
     for (int i = 0; i < 2; ++i) {
-        if (c->dev_leaves[i]) hipFree(c->dev_leaves[i]);
-        if (c->dev_idx[i]) hipFree(c->dev_idx[i]);
-        if (c->pin_out[i]) hipHostFree(c->pin_out[i]);
-        c->dev_leaves[i] = nullptr, c->dev_idx[i] = nullptr, c->pin_out[i] = nullptr;
+        if (int rc = ensure(c, c->dev_leaves[i], (size_t)n * 512, "the device leaf slot")) return rc;
+        if (int rc = ensure(c, c->dev_idx[i], (size_t)n * 64, "the device index slot")) return rc;
+        if (int rc = ensure(c, c->pin_out[i], (size_t)n * 2048, "the pinned result slot")) return rc;
     }
-    c->dev_io_leaves = 0;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipMalloc(&c->dev_leaves[i], (size_t)n * 512 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->dev_idx[i], (size_t)n * 64));
-        HIPCHK(c, hipHostMalloc(&c->pin_out[i], (size_t)n * 512 * sizeof(float), hipHostMallocDefault));
-    }
-    c->dev_io_leaves = n;
     return VQHIP_OK;
 }
 
 // pinned input staging (leaf blocks: gathered leaf buffers or the caller's pageable block; index blocks of single-chunk decodes)
 int ensure_stage(vqhip_codec* c, size_t bytes)
 {
-    if (c->pin_in_bytes >= bytes) return VQHIP_OK;
-    for (int i = 0; i < 2; ++i) {
-        if (c->pin_in[i]) hipHostFree(c->pin_in[i]);
-        c->pin_in[i] = nullptr;
-    }
-    c->pin_in_bytes = 0;
-    for (int i = 0; i < 2; ++i) HIPCHK(c, hipHostMalloc(&c->pin_in[i], bytes, hipHostMallocDefault));
-    c->pin_in_bytes = bytes;
+    for (int i = 0; i < 2; ++i)
+        if (int rc = ensure(c, c->pin_in[i], bytes, "the pinned input stage")) return rc;
     return VQHIP_OK;
 }
 
@@ -1925,38 +1889,11 @@ void vqhip_destroy(vqhip_codec* c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto& kv : c->dw) hipFree(kv.second);
-    if (c->ws) hipFree(c->ws);
-    if (c->tr_z) hipFree(c->tr_z);
-    if (c->tr_idx) hipFree(c->tr_idx);
-    if (c->tr_part) hipFree(c->tr_part);
-    if (c->ft_refrag_jobs) hipFree(c->ft_refrag_jobs);
-    if (c->ft_P) hipFree(c->ft_P);
-    if (c->ft_M) hipFree(c->ft_M);
-    if (c->ft_V) hipFree(c->ft_V);
-    if (c->ft_ws) hipFree(c->ft_ws);
-    if (c->ft_part) hipFree(c->ft_part);
     for (hipEvent_t e : c->ft_ev) hipEventDestroy(e);
     if (c->ft_side) hipStreamDestroy(c->ft_side);
     if (c->ft_red) hipStreamDestroy(c->ft_red);
     if (c->ft_red_shared) hipStreamDestroy(c->ft_red_shared);
-    if (c->tr_recon) hipFree(c->tr_recon);
-    if (c->tr_loss_part) hipFree(c->tr_loss_part);
-    if (c->bd_recon) hipFree(c->bd_recon);
-    if (c->bd_idx) hipFree(c->bd_idx);
-    if (c->bd_ids) hipFree(c->bd_ids);
-    if (c->bd_scan) hipFree(c->bd_scan);
-    if (c->rate_hist) hipFree(c->rate_hist);
     for (int i = 0; i < 2; ++i) {
-        if (c->bd_err[i]) hipFree(c->bd_err[i]);
-        if (c->bd_pin_err[i]) hipHostFree(c->bd_pin_err[i]);
-        if (c->rs_class[i]) hipFree(c->rs_class[i]);
-        if (c->rs_off[i]) hipFree(c->rs_off[i]);
-        if (c->rs_payload[i]) hipFree(c->rs_payload[i]);
-        if (c->rs_pin[i]) hipHostFree(c->rs_pin[i]);
-        if (c->dev_leaves[i]) hipFree(c->dev_leaves[i]);
-        if (c->dev_idx[i]) hipFree(c->dev_idx[i]);
-        if (c->pin_out[i]) hipHostFree(c->pin_out[i]);
-        if (c->pin_in[i]) hipHostFree(c->pin_in[i]);
         if (c->ev_in[i]) hipEventDestroy(c->ev_in[i]);
         if (c->ev_done[i]) hipEventDestroy(c->ev_done[i]);
         if (c->ev_out[i]) hipEventDestroy(c->ev_out[i]);
@@ -1968,7 +1905,7 @@ void vqhip_destroy(vqhip_codec* c)
         hipEventDestroy(t.stop);
     }
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the buffers go in the struct's destructor, with the device still current
 }
 
 int vqhip_latent_shape(const vqhip_codec* c, int64_t out[3])
@@ -2008,7 +1945,7 @@ int vqhip_reserve(vqhip_codec* c, int64_t n)
     return rc;
 }
 
-int64_t vqhip_workspace_bytes(const vqhip_codec* c) { return c ? (int64_t)c->ws_bytes : -1; }
+int64_t vqhip_workspace_bytes(const vqhip_codec* c) { return c ? (int64_t)c->ws.bytes() : -1; }
 
 int64_t vqhip_chunk_leaves(const vqhip_codec* c) { return c ? c->chunk : -1; }
 
@@ -2138,25 +2075,11 @@ int vqhip_train_vq_stats_device(vqhip_codec* c, const float* d_leaves, int64_t n
     if (n > c->chunk) return fail(c, VQHIP_ERR_INVALID, "train_vq_stats: a training batch may not exceed the chunk size (" + std::to_string(c->chunk) + " leaves)");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if ((!d_latent || !d_idx) && c->tr_leaves < n) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (c->tr_z) hipFree(c->tr_z);
-        if (c->tr_idx) hipFree(c->tr_idx);
-        c->tr_z = nullptr, c->tr_idx = nullptr, c->tr_leaves = 0;
-        HIPCHK(c, hipMalloc(&c->tr_z, (size_t)n * 64 * 128 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->tr_idx, (size_t)n * 64));
-        c->tr_leaves = n;
+    if (!d_latent || !d_idx) {
+        if (int rc = ensure(c, c->tr_z, (size_t)n * 64 * 128, "the training latents")) return rc;
+        if (int rc = ensure(c, c->tr_idx, (size_t)n * 64, "the training indices")) return rc;
     }
-    {
-        const size_t need = ema_scratch_bytes((int)((n * 64 + VQ_SEG_ROWS - 1) / VQ_SEG_ROWS));
-        if (c->tr_part_bytes < need) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (c->tr_part) hipFree(c->tr_part);
-            c->tr_part = nullptr, c->tr_part_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->tr_part, need));
-            c->tr_part_bytes = need;
-        }
-    }
+    if (int rc = ensure(c, c->tr_part, ema_scratch_bytes((int)((n * 64 + VQ_SEG_ROWS - 1) / VQ_SEG_ROWS)), "the codebook statistics partials")) return rc;
     float* z = d_latent ? d_latent : c->tr_z;
     uint8_t* idx = d_idx ? d_idx : c->tr_idx;
     int rc = encode_chunk(c, d_leaves, n, idx, s, z);
@@ -2182,16 +2105,10 @@ int vqhip_train_eval_device(vqhip_codec* c, const float* d_leaves, int64_t n, fl
     if ((rc = ensure_tables(c))) return rc;  // the decoder's stem table follows the live codebook
     float* recon = d_recon;
     if (!recon) {
-        if (c->tr_recon_leaves < n) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (c->tr_recon) hipFree(c->tr_recon);
-            c->tr_recon = nullptr, c->tr_recon_leaves = 0;
-            HIPCHK(c, hipMalloc(&c->tr_recon, (size_t)n * 512 * sizeof(float)));
-            c->tr_recon_leaves = n;
-        }
+        if ((rc = ensure(c, c->tr_recon, (size_t)n * 512, "the evaluation's reconstruction"))) return rc;
         recon = c->tr_recon;
     }
-    if (!c->tr_loss_part) HIPCHK(c, hipMalloc(&c->tr_loss_part, (size_t)RL_BLOCKS * 2 * sizeof(double)));
+    if ((rc = ensure(c, c->tr_loss_part, (size_t)RL_BLOCKS * 2, "the loss partials"))) return rc;
     if ((rc = decode_chunk(c, c->tr_idx, n, recon, s))) return rc;
     Launcher L{c, s, n};
     L.run("train_recon_loss", [&] {

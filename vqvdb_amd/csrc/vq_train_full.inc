@@ -28,17 +28,12 @@ int ensure_train_workspace(vqhip_codec* c, int64_t n_leaves)
 {
     const int64_t tiles = (n_leaves + 31) / 32;
     if (tiles <= c->ft_tiles) return VQHIP_OK;
-    HIPCHK(c, hipDeviceSynchronize());
-    if (c->ft_ws) hipFree(c->ft_ws);
-    c->ft_ws = nullptr, c->ft_tiles = 0;
     auto bytes = [&](const ActSpec& a) { return (((a.C ? (size_t)a.C * a.NP : (size_t)a.NP) * sizeof(float) * 32 * tiles) + 255) / 256 * 256; };
     size_t total = 0;
     for (const ActSpec& a : kTrainActs) total += bytes(a);
-    hipError_t e = hipMalloc(&c->ft_ws, total);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();   // sticky until read: the next launch check must not see this allocation's error
-        c->ft_ws = nullptr;
-        return fail(c, VQHIP_ERR_NOMEM, std::string("training workspace hipMalloc failed: ") + hipGetErrorString(e));
+    if (int rc = ensure(c, c->ft_ws, total, [](hipError_t e) { return std::string("training workspace hipMalloc failed: ") + hipGetErrorString(e); })) {
+        if (!c->ft_ws) c->ft_tiles = 0;   // (a failed synchronise leaves the old block and its layout)
+        return rc;
     }
     size_t off = 0;
     for (const ActSpec& a : kTrainActs) {
@@ -77,11 +72,12 @@ int refrag_all(vqhip_codec* c, hipStream_t s)
     // The job list is built once (the tables are allocated on the first pass and never move, the parameters live in ft_P) and kept on the
     // device; every later call is ONE launch of refrag_multi_k.
     if (c->ft_refrag_jobs && c->ft_refrag_P != c->ft_P) {   // the cached table bakes in addresses inside the parameter block: rebuild if that moved
-        (void)hipFree(c->ft_refrag_jobs);
-        c->ft_refrag_jobs = nullptr, c->ft_refrag_n = c->ft_refrag_wgs = 0;
+        HIPCHK(c, hipDeviceSynchronize());
+        c->ft_refrag_jobs.reset();
+        c->ft_refrag_n = c->ft_refrag_wgs = 0;
     }
     if (c->ft_refrag_jobs) {
-        hipLaunchKernelGGL(refrag_multi_k, dim3(c->ft_refrag_wgs), dim3(256), 0, s, (const RefragJob*)c->ft_refrag_jobs, c->ft_refrag_n);
+        hipLaunchKernelGGL(refrag_multi_k, dim3(c->ft_refrag_wgs), dim3(256), 0, s, (const RefragJob*)c->ft_refrag_jobs.get(), c->ft_refrag_n);
         HIPCHK(c, hipGetLastError());
         return VQHIP_OK;
     }
@@ -154,17 +150,14 @@ int refrag_all(vqhip_codec* c, hipStream_t s)
 #undef R16G
     // the list is published (pointer, count, grid) only once it is on the device: a failure on the way leaves the handle without one,
     // and the next step builds it again
-    void* djobs = nullptr;
-    HIPCHK(c, hipMalloc(&djobs, jobs.size() * sizeof(RefragJob)));
+    DevBuf<unsigned char> djobs;
+    if ((rc = ensure(c, djobs, jobs.size() * sizeof(RefragJob), "the refrag job list"))) return rc;
     hipError_t je = hipMemcpyAsync(djobs, jobs.data(), jobs.size() * sizeof(RefragJob), hipMemcpyHostToDevice, s);
     if (je == hipSuccess) je = hipStreamSynchronize(s);   // (jobs is a local)
-    if (je != hipSuccess) {
-        (void)hipFree(djobs);
-        return fail(c, VQHIP_ERR_DEVICE, std::string("refrag job list upload: ") + hipGetErrorString(je));
-    }
-    c->ft_refrag_jobs = static_cast<decltype(c->ft_refrag_jobs)>(djobs);
+    if (je != hipSuccess) return fail(c, VQHIP_ERR_DEVICE, std::string("refrag job list upload: ") + hipGetErrorString(je));
+    c->ft_refrag_jobs = std::move(djobs);
     c->ft_refrag_n = (int)jobs.size(), c->ft_refrag_wgs = wgs, c->ft_refrag_P = c->ft_P;
-    hipLaunchKernelGGL(refrag_multi_k, dim3(wgs), dim3(256), 0, s, (const RefragJob*)c->ft_refrag_jobs, c->ft_refrag_n);
+    hipLaunchKernelGGL(refrag_multi_k, dim3(wgs), dim3(256), 0, s, (const RefragJob*)c->ft_refrag_jobs.get(), c->ft_refrag_n);
     HIPCHK(c, hipGetLastError());
     return VQHIP_OK;
 }
@@ -316,15 +309,8 @@ int fulltrain_forward(vqhip_codec* c, const float* d_leaves, int64_t n, hipStrea
 {
     int rc = ensure_train_workspace(c, n);
     if (rc) return rc;
-    if (c->tr_leaves < n) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        if (c->tr_z) hipFree(c->tr_z);
-        if (c->tr_idx) hipFree(c->tr_idx);
-        c->tr_z = nullptr, c->tr_idx = nullptr, c->tr_leaves = 0;
-        HIPCHK(c, hipMalloc(&c->tr_z, (size_t)n * 64 * 128 * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->tr_idx, (size_t)n * 64));
-        c->tr_leaves = n;
-    }
+    if ((rc = ensure(c, c->tr_z, (size_t)n * 64 * 128, "the training latents"))) return rc;
+    if ((rc = ensure(c, c->tr_idx, (size_t)n * 64, "the training indices"))) return rc;
     if ((rc = ensure_workspace(c, n))) return rc;
     // The folded tail depends on the parameters only: it is rebuilt on the second stream while the encoder runs (0.08 ms off the chain).
     c->ft_ev_next = 0;   // (a step starts here: rewind the event pool)
@@ -367,15 +353,7 @@ int fulltrain_forward(vqhip_codec* c, const float* d_leaves, int64_t n, hipStrea
         // which is idle until the backward pass, instead of at the head of the weight-gradient queue (0.2 ms of its 2.8 ms at 2048 leaves)
         const int64_t rows = n * 64;
         const int n_seg = (int)((rows + VQ_SEG_ROWS - 1) / VQ_SEG_ROWS);
-        const size_t need = ema_scratch_bytes(n_seg);
-        if (c->tr_part_bytes < need) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            HIPCHK(c, hipStreamSynchronize(ws));
-            if (c->tr_part) hipFree(c->tr_part);
-            c->tr_part = nullptr, c->tr_part_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->tr_part, need));
-            c->tr_part_bytes = need;
-        }
+        if ((rc = ensure(c, c->tr_part, ema_scratch_bytes(n_seg), "the codebook statistics partials"))) return rc;
         L.run_on(ws, "ft_vq_stats", [&] { launch_vq_ema(c, ws, c->tr_z, c->tr_idx, rows, n_seg, d_aux); });
         if (ema_done) *ema_done = true;
     }
@@ -510,14 +488,8 @@ int ensure_parts(vqhip_codec* c, int nt, PartBufs& pb)
     const size_t gnp = (size_t)nt * 32 * 2 * GN_PART_CHANNELS;
     const size_t dfp = (size_t)nt * 32 * DEF_PART_CHANNELS;
     const size_t need = (wg + 4 * ch + 2 * sm + gnp + dfp) * sizeof(float);
-    if (c->ft_part_bytes < need) {
-        HIPCHK(c, hipDeviceSynchronize());
-        if (c->ft_part) hipFree(c->ft_part);
-        c->ft_part = nullptr, c->ft_part_bytes = 0;
-        HIPCHK(c, hipMalloc(&c->ft_part, need));
-        c->ft_part_bytes = need;
-    }
-    pb.wg = reinterpret_cast<float*>(c->ft_part);
+    if (int rc = ensure(c, c->ft_part, need, "the partial-gradient scratch")) return rc;
+    pb.wg = reinterpret_cast<float*>(c->ft_part.get());
     pb.chA = pb.wg + wg;
     pb.chB = pb.chA + ch;
     pb.small = pb.chB + ch;
@@ -1072,11 +1044,9 @@ int vqhip_fulltrain_begin(vqhip_codec* c)
     int rc = c->training ? VQHIP_OK : vqhip_train_begin(c, nullptr, nullptr);
     if (rc) return rc;
     const size_t np = c->h_params.size();
-    if (!c->ft_P) {
-        HIPCHK(c, hipMalloc(&c->ft_P, np * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->ft_M, np * sizeof(float)));
-        HIPCHK(c, hipMalloc(&c->ft_V, np * sizeof(float)));
-    }
+    if ((rc = ensure(c, c->ft_P, np, "the training parameters"))) return rc;
+    if ((rc = ensure(c, c->ft_M, np, "the first AdamW moments"))) return rc;
+    if ((rc = ensure(c, c->ft_V, np, "the second AdamW moments"))) return rc;
     HIPCHK(c, hipMemcpy(c->ft_P, c->h_params.data(), np * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemset(c->ft_M, 0, np * sizeof(float)));
     HIPCHK(c, hipMemset(c->ft_V, 0, np * sizeof(float)));
@@ -1153,15 +1123,8 @@ int vqhip_fulltrain_fwdbwd_overlap_device(vqhip_codec* c, const float* d_leaves,
         // codebook statistics of this batch (same kernels as stage 1) and the reconstruction-loss sums
         const int64_t rows = n * 64;
         const int n_seg = (int)((rows + VQ_SEG_ROWS - 1) / VQ_SEG_ROWS);
-        const size_t need = ema_scratch_bytes(n_seg);
-        if (c->tr_part_bytes < need) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            if (c->tr_part) hipFree(c->tr_part);
-            c->tr_part = nullptr, c->tr_part_bytes = 0;
-            HIPCHK(c, hipMalloc(&c->tr_part, need));
-            c->tr_part_bytes = need;
-        }
-        if (!c->tr_loss_part) HIPCHK(c, hipMalloc(&c->tr_loss_part, (size_t)RL_BLOCKS * 2 * sizeof(double)));
+        if (int rc = ensure(c, c->tr_part, ema_scratch_bytes(n_seg), "the codebook statistics partials")) return rc;
+        if (int rc = ensure(c, c->tr_loss_part, (size_t)RL_BLOCKS * 2, "the loss partials")) return rc;
         // (second stream: nothing in the backward pass needs them; Bwd::join at the end of the step covers them)
         hipStream_t ws = B.ws;
         B.fork();

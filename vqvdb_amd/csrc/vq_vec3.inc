@@ -12,47 +12,41 @@ struct vqhip_vec3_codec {
     std::map<std::string, float*> w;   // device weights / fragments
     int64_t chunk = 16384;
     bool chunk_fitted = false;
-    float* ws = nullptr;
-    int64_t ws_leaves = 0;
-    float* io_leaves = nullptr;        // host entry points: [chunk][512][3]
-    uint16_t* io_idx = nullptr;        // [chunk][64]
-    int64_t io_n = 0;
+    DevBuf<float> ws;                  // V3_LEAF_FLOATS per leaf; v3_ws lays it out for the leaves it holds
+    DevBuf<float> io_leaves;           // host entry points: [chunk][512][3]
+    DevBuf<uint16_t> io_idx;           // [chunk][64]
     bool debug = false;
     // bf16-operand inference mode (vq_vec3_bf16.inc): VQHIP_VEC3_PRECISION_*; the bf16 fragment tables exist once bf_ready
     int precision = 0;
     bool bf_ready = false;
     // codebook training (vq_vec3_train.inc): set by vqhip_vec3_train_begin
     bool training = false;
-    float* tr_cs = nullptr;            // cluster_size [K]
-    float* tr_avg = nullptr;           // embed_avg [K][64]
-    unsigned char* tr_ws = nullptr;    // training workspace of tr_leaves leaves (v3t_ws_bytes)
+    DevBuf<float> tr_cs;               // cluster_size [K]
+    DevBuf<float> tr_avg;              // embed_avg [K][64]
+    DevBuf<unsigned char> tr_ws;       // training workspace, laid out for tr_leaves leaves (v3t_layout)
     int64_t tr_leaves = 0;
     // full training (vq_vec3_fulltrain.inc): set by vqhip_vec3_fulltrain_begin; P, M, V live in w ("ft.P", "ft.M", "ft.V")
     bool ft_on = false;
     float *ft_P = nullptr, *ft_M = nullptr, *ft_V = nullptr;
-    float* ft_ws = nullptr;            // activations, gradients and partials of ft_leaves leaves (v3f_ws_bytes)
+    DevBuf<float> ft_ws;               // activations, gradients and partials, laid out for ft_leaves leaves (v3f_layout)
     int64_t ft_leaves = 0;
     // error-bounded round trip (vq_vec3_bounded.inc)
-    int64_t* bd_scan = nullptr;        // selection: per-block counts / offsets [bd_scan_n]
-    int64_t bd_scan_n = 0;
-    float* bd_err = nullptr;           // host entry point: leaf errors [bd_n][2]
-    int64_t* bd_ids = nullptr;         // host entry point: outlier ids [bd_n], then their count
-    int64_t bd_n = 0;
+    DevBuf<int64_t> bd_scan;           // selection: per-block counts / offsets
+    DevBuf<float> bd_err;              // host entry point: leaf errors [m][2]
+    DevBuf<int64_t> bd_ids;            // host entry point: outlier ids [m], then their count
     // quantised residuals (vq_vec3_residual.inc), host pair: one chunk's reconstruction, leaf errors, codes, offsets, payload
-    float* rs_recon = nullptr;         // [rs_n][512][3]
-    float* rs_err = nullptr;           // [rs_n][2]
-    uint16_t* rs_code = nullptr;       // [rs_n]
-    int64_t* rs_off = nullptr;         // [rs_n + 1]
-    uint8_t* rs_payload = nullptr;     // rs_n * 6144 bytes
-    int64_t rs_n = 0;
-    // size sweep (vq_vec3_rate.inc), host calls: the histogram [64][51], allocated on first use
-    int64_t* rate_hist = nullptr;
-    // active-voxel masks (vq_vec3_mask.inc), host calls: one chunk's masks [mk_n][8]
-    uint64_t* mk_mask = nullptr;
-    int64_t mk_n = 0;
+    DevBuf<float> rs_recon;            // [m][512][3]
+    DevBuf<float> rs_err;              // [m][2]
+    DevBuf<uint16_t> rs_code;          // [m]
+    DevBuf<int64_t> rs_off;            // [m + 1]
+    DevBuf<uint8_t> rs_payload;        // m * 6144 bytes
+    // size sweep (vq_vec3_rate.inc), host calls: the histogram [64][51]
+    DevBuf<int64_t> rate_hist;
+    // active-voxel masks (vq_vec3_mask.inc), host calls: one chunk's masks [m][8]
+    DevBuf<uint64_t> mk_mask;
     struct Dbg {
-        float* p = nullptr;
-        int64_t cap = 0, n = 0;
+        DevBuf<float> p;
+        int64_t n = 0;
         int floats = 0;                // per leaf
     };
     std::map<std::string, Dbg> dbg;
@@ -85,7 +79,7 @@ struct V3Ws {
 };
 V3Ws v3_ws(const vqhip_vec3_codec* c)
 {
-    const int64_t L = c->ws_leaves;
+    const int64_t L = (int64_t)c->ws.capacity() / V3_LEAF_FLOATS;
     V3Ws r;
     r.a8 = c->ws;
     r.b8 = r.a8 + L * 64 * 512;
@@ -304,21 +298,9 @@ int v3_init_attrs(vqhip_vec3_codec* c)
 
 int v3_ensure_ws(vqhip_vec3_codec* c, int64_t m)
 {
-    if (m <= c->ws_leaves) return VQHIP_OK;
-    if (c->ws) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->ws);
-        c->ws = nullptr;
-        c->ws_leaves = 0;
-    }
-    if (hipMalloc(&c->ws, (size_t)m * V3_LEAF_FLOATS * sizeof(float)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->ws = nullptr;
-        c->chunk_fitted = false;   // re-fit the chunk to the free memory at the next call
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3: cannot allocate the workspace of " + std::to_string(m) + " leaves");
-    }
-    c->ws_leaves = m;
-    return VQHIP_OK;
+    const int rc = ensure(c, c->ws, (size_t)m * V3_LEAF_FLOATS, [&](hipError_t) { return "vec3: cannot allocate the workspace of " + std::to_string(m) + " leaves"; });
+    if (rc) c->chunk_fitted = false;   // re-fit the chunk to the free memory at the next call
+    return rc;
 }
 
 size_t v3t_ws_bytes(int64_t leaves, int k_codes);   // vq_vec3_train.inc: training workspace of a chunk (0 for 0 leaves)
@@ -329,9 +311,7 @@ void v3_fit_chunk(vqhip_vec3_codec* c)
 {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return;
-    free_b += (size_t)c->ws_leaves * V3_LEAF_FLOATS * sizeof(float) + (size_t)c->io_n * V3_IO_BYTES;
-    if (c->training) free_b += v3t_ws_bytes(c->tr_leaves, c->k_codes);
-    if (c->ft_on) free_b += v3f_ws_bytes(c->ft_leaves);
+    free_b += c->ws.bytes() + c->io_leaves.bytes() + c->io_idx.bytes() + c->tr_ws.bytes() + c->ft_ws.bytes();   // what this handle holds can be re-used
     auto need = [&](int64_t m) {
         return (size_t)m * (V3_LEAF_FLOATS * sizeof(float) + V3_IO_BYTES) + (c->training ? v3t_ws_bytes(m, c->k_codes) : 0) +
                (c->ft_on ? v3f_ws_bytes(m) : 0);
@@ -346,16 +326,8 @@ int v3_keep(vqhip_vec3_codec* c, const char* name, const float* src, int floats,
 {
     if (!c->debug) return VQHIP_OK;
     auto& d = c->dbg[name];
-    if (d.cap < m || d.floats != floats) {
-        if (d.p) {
-            HIPCHK(c, hipStreamSynchronize(s));
-            hipFree(d.p);
-            d.p = nullptr;
-        }
-        HIPCHK(c, hipMalloc(&d.p, (size_t)m * floats * sizeof(float)));
-        d.cap = m;
-        d.floats = floats;
-    }
+    if (int rc = ensure(c, d.p, (size_t)m * floats, "a debug activation")) return rc;
+    d.floats = floats;
     d.n = m;
     HIPCHK(c, hipMemcpyAsync(d.p, src, (size_t)m * floats * sizeof(float), hipMemcpyDeviceToDevice, s));
     return VQHIP_OK;
@@ -491,16 +463,9 @@ int v3_decode_mode(vqhip_vec3_codec* c, const uint16_t* idx, int64_t m, float* o
 
 int v3_ensure_io(vqhip_vec3_codec* c, int64_t m)
 {
-    if (m <= c->io_n) return VQHIP_OK;
-    if (c->io_leaves) hipFree(c->io_leaves), c->io_leaves = nullptr;
-    if (c->io_idx) hipFree(c->io_idx), c->io_idx = nullptr;
-    c->io_n = 0;
-    if (hipMalloc(&c->io_leaves, (size_t)m * 1536 * sizeof(float)) != hipSuccess || hipMalloc(&c->io_idx, (size_t)m * 64 * sizeof(uint16_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3: cannot allocate the I/O buffers of " + std::to_string(m) + " leaves");
-    }
-    c->io_n = m;
-    return VQHIP_OK;
+    auto nomem = [&](hipError_t) { return "vec3: cannot allocate the I/O buffers of " + std::to_string(m) + " leaves"; };
+    if (int rc = ensure(c, c->io_leaves, (size_t)m * 1536, nomem)) return rc;
+    return ensure(c, c->io_idx, (size_t)m * 64, nomem);
 }
 
 int v3_prepare(vqhip_vec3_codec* c)
@@ -573,27 +538,8 @@ void vqhip_vec3_destroy(vqhip_vec3_codec* c)
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     for (auto& kv : c->w) hipFree(kv.second);
-    for (auto& kv : c->dbg)
-        if (kv.second.p) hipFree(kv.second.p);
-    if (c->ws) hipFree(c->ws);
-    if (c->io_leaves) hipFree(c->io_leaves);
-    if (c->io_idx) hipFree(c->io_idx);
-    if (c->tr_cs) hipFree(c->tr_cs);
-    if (c->tr_avg) hipFree(c->tr_avg);
-    if (c->tr_ws) hipFree(c->tr_ws);
-    if (c->ft_ws) hipFree(c->ft_ws);
-    if (c->bd_scan) hipFree(c->bd_scan);
-    if (c->bd_err) hipFree(c->bd_err);
-    if (c->bd_ids) hipFree(c->bd_ids);
-    if (c->rs_recon) hipFree(c->rs_recon);
-    if (c->rs_err) hipFree(c->rs_err);
-    if (c->rs_code) hipFree(c->rs_code);
-    if (c->rs_off) hipFree(c->rs_off);
-    if (c->rs_payload) hipFree(c->rs_payload);
-    if (c->rate_hist) hipFree(c->rate_hist);
-    if (c->mk_mask) hipFree(c->mk_mask);
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // the buffers go in the struct's destructor, with the device still current
 }
 
 int vqhip_vec3_model_info(const vqhip_vec3_codec* c, int64_t* num_codes, int64_t* embedding_dim, int64_t latent[3])

@@ -29,21 +29,8 @@ int v3e_roundtrip_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uin
 
 int v3e_ensure_scan(vqhip_vec3_codec* c, int64_t nb)
 {
-    if (nb <= c->bd_scan_n) return VQHIP_OK;
-    if (c->bd_scan) {
-        HIPCHK(c, hipDeviceSynchronize());   // an earlier selection on any stream may still read it
-        hipFree(c->bd_scan);
-        c->bd_scan = nullptr;
-        c->bd_scan_n = 0;
-    }
     nb = std::max<int64_t>(nb, V3_MAX_CHUNK / v3e::SEL_BLOCK);
-    if (hipMalloc(&c->bd_scan, (size_t)nb * sizeof(int64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->bd_scan = nullptr;
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 select_outliers: cannot allocate the scan buffer of " + std::to_string(nb) + " blocks");
-    }
-    c->bd_scan_n = nb;
-    return VQHIP_OK;
+    return ensure(c, c->bd_scan, (size_t)nb, [&](hipError_t) { return "vec3 select_outliers: cannot allocate the scan buffer of " + std::to_string(nb) + " blocks"; });
 }
 
 int v3e_select(vqhip_vec3_codec* c, const float* err, int64_t n, float tol, int64_t* ids, int64_t* count, hipStream_t s)
@@ -59,17 +46,9 @@ int v3e_select(vqhip_vec3_codec* c, const float* err, int64_t n, float tol, int6
 // host entry point: leaf errors, outlier ids and their count of one chunk (ids [m] and the count behind them)
 int v3e_ensure_host(vqhip_vec3_codec* c, int64_t m)
 {
-    if (m <= c->bd_n) return VQHIP_OK;
-    if (c->bd_err) hipFree(c->bd_err), c->bd_err = nullptr;
-    if (c->bd_ids) hipFree(c->bd_ids), c->bd_ids = nullptr;
-    c->bd_n = 0;
-    if (hipMalloc(&c->bd_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float)) != hipSuccess ||
-        hipMalloc(&c->bd_ids, (size_t)(m + 1) * sizeof(int64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 compress_bounded: cannot allocate the error buffers of " + std::to_string(m) + " leaves");
-    }
-    c->bd_n = m;
-    return VQHIP_OK;
+    auto nomem = [&](hipError_t) { return "vec3 compress_bounded: cannot allocate the error buffers of " + std::to_string(m) + " leaves"; };
+    if (int rc = ensure(c, c->bd_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS, nomem)) return rc;
+    return ensure(c, c->bd_ids, (size_t)m + 1, nomem);
 }
 
 }  // namespace
@@ -123,7 +102,7 @@ int vqhip_vec3_compress_bounded(vqhip_vec3_codec* c, const float* leaves, int64_
         const int64_t m = std::min(c->chunk, n - o);
         if (int rc = v3_ensure_io(c, m)) return rc;
         if (int rc = v3e_ensure_host(c, m)) return rc;
-        int64_t* d_count = c->bd_ids + c->bd_n;
+        int64_t* d_count = c->bd_ids + m;
         HIPCHK(c, hipMemcpyAsync(c->io_leaves, leaves + o * 1536, (size_t)m * 1536 * sizeof(float), hipMemcpyHostToDevice, c->stream));
         if (int rc = v3e_roundtrip_chunk(c, c->io_leaves, m, c->io_idx, nullptr, c->bd_err, c->stream)) return rc;
         if (int rc = v3e_select(c, c->bd_err, m, tol, c->bd_ids, d_count, c->stream)) return rc;

@@ -170,21 +170,13 @@ int v3f_require(vqhip_vec3_codec* c, const char* what)
     return VQHIP_OK;
 }
 
-int v3f_ensure_ws(vqhip_vec3_codec* c, int64_t m, hipStream_t s)
+int v3f_ensure_ws(vqhip_vec3_codec* c, int64_t m)
 {
     if (m <= c->ft_leaves) return VQHIP_OK;
-    if (c->ft_ws) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->ft_ws);
-        c->ft_ws = nullptr;
-        c->ft_leaves = 0;
-    }
-    if (hipMalloc(&c->ft_ws, v3f_ws_bytes(m)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->ft_ws = nullptr;
+    if (int rc = ensure(c, c->ft_ws, v3f_ws_bytes(m) / sizeof(float), [&](hipError_t) { return "vec3 full training: cannot allocate the workspace of " + std::to_string(m) + " leaves"; })) {
+        if (!c->ft_ws) c->ft_leaves = 0;   // (a failed synchronise leaves the old block and its layout)
         c->chunk_fitted = false;
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 full training: cannot allocate the workspace of " + std::to_string(m) + " leaves");
+        return rc;
     }
     c->ft_leaves = m;
     return VQHIP_OK;
@@ -496,7 +488,7 @@ int vqhip_vec3_fulltrain_forward_device(vqhip_vec3_codec* c, const float* leaves
     if (int rc = v3f_check_batch(c, "vec3 fulltrain_forward", leaves_dev, n)) return rc;
     if (n == 0) return VQHIP_OK;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (int rc = v3f_ensure_ws(c, n, s)) return rc;
+    if (int rc = v3f_ensure_ws(c, n)) return rc;
     V3FWs F;
     if (int rc = v3f_forward(c, leaves_dev, n, s, F)) return rc;
     if (indices_dev) HIPCHK(c, hipMemcpyAsync(indices_dev, F.idx, (size_t)n * 64 * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
@@ -522,8 +514,8 @@ int vqhip_vec3_fulltrain_fwdbwd_device(vqhip_vec3_codec* c, const float* leaves_
         return VQHIP_OK;
     }
     if (int rc = v3_ensure_ws(c, n)) return rc;
-    if (int rc = v3t_ensure_ws(c, n, s)) return rc;
-    if (int rc = v3f_ensure_ws(c, n, s)) return rc;
+    if (int rc = v3t_ensure_ws(c, n)) return rc;
+    if (int rc = v3f_ensure_ws(c, n)) return rc;
     const V3TWs T = v3t_layout(c->tr_ws, c->tr_leaves, c->k_codes);
     V3FWs F;
     if (int rc = v3f_forward(c, leaves_dev, n, s, F)) return rc;

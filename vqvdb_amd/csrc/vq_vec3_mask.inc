@@ -43,16 +43,7 @@ int v3m_sweep(vqhip_vec3_codec* c, const float* d_leaves, const float* d_recon, 
 int v3m_ensure_host(vqhip_vec3_codec* c, int64_t m)
 {
     if (int rc = v3r_ensure_host(c, m)) return rc;
-    if (m <= c->mk_n) return VQHIP_OK;
-    if (c->mk_mask) hipFree(c->mk_mask), c->mk_mask = nullptr;
-    c->mk_n = 0;
-    if (hipMalloc(&c->mk_mask, (size_t)m * 64) != hipSuccess) {
-        (void)hipGetLastError();
-        c->mk_mask = nullptr;
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 mask: cannot allocate the masks of " + std::to_string(m) + " leaves");
-    }
-    c->mk_n = m;
-    return VQHIP_OK;
+    return ensure(c, c->mk_mask, (size_t)m * 8, [&](hipError_t) { return "vec3 mask: cannot allocate the masks of " + std::to_string(m) + " leaves"; });
 }
 
 // one chunk of the host calls, leaves and masks from the caller's arrays: the round trip with a stored reconstruction, then the

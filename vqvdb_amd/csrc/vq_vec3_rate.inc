@@ -27,7 +27,7 @@ int v3rate_sweep(vqhip_vec3_codec* c, const float* d_leaves, const float* d_reco
 // the handle's histogram, cleared on its stream
 int v3rate_begin(vqhip_vec3_codec* c)
 {
-    if (!c->rate_hist) HIPCHK(c, hipMalloc(&c->rate_hist, V3RATE_HIST_BYTES));
+    if (int rc = ensure(c, c->rate_hist, V3RATE_HIST_BYTES / sizeof(int64_t), "the size-sweep histogram")) return rc;
     HIPCHK(c, hipMemsetAsync(c->rate_hist, 0, V3RATE_HIST_BYTES, c->stream));
     return VQHIP_OK;
 }

@@ -27,30 +27,15 @@ int v3r_apply(vqhip_vec3_codec* c, float* d_leaves, int64_t n, float tol, const 
     return v3_launch_check(c, "vec3 residual_apply");
 }
 
-void v3r_free(vqhip_vec3_codec* c)
-{
-    if (c->rs_recon) hipFree(c->rs_recon), c->rs_recon = nullptr;
-    if (c->rs_err) hipFree(c->rs_err), c->rs_err = nullptr;
-    if (c->rs_code) hipFree(c->rs_code), c->rs_code = nullptr;
-    if (c->rs_off) hipFree(c->rs_off), c->rs_off = nullptr;
-    if (c->rs_payload) hipFree(c->rs_payload), c->rs_payload = nullptr;
-    c->rs_n = 0;
-}
-
 // host pair: reconstruction, leaf errors, codes, offsets and payload of one chunk
 int v3r_ensure_host(vqhip_vec3_codec* c, int64_t m)
 {
-    if (m <= c->rs_n) return VQHIP_OK;
-    v3r_free(c);
-    if (hipMalloc(&c->rs_recon, (size_t)m * 6144) != hipSuccess || hipMalloc(&c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float)) != hipSuccess ||
-        hipMalloc(&c->rs_code, (size_t)m * sizeof(uint16_t)) != hipSuccess || hipMalloc(&c->rs_off, (size_t)(m + 1) * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc(&c->rs_payload, (size_t)m * 6144) != hipSuccess) {
-        (void)hipGetLastError();
-        v3r_free(c);
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 residual: cannot allocate the record buffers of " + std::to_string(m) + " leaves");
-    }
-    c->rs_n = m;
-    return VQHIP_OK;
+    auto nomem = [&](hipError_t) { return "vec3 residual: cannot allocate the record buffers of " + std::to_string(m) + " leaves"; };
+    if (int rc = ensure(c, c->rs_recon, (size_t)m * 1536, nomem)) return rc;
+    if (int rc = ensure(c, c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS, nomem)) return rc;
+    if (int rc = ensure(c, c->rs_code, (size_t)m, nomem)) return rc;
+    if (int rc = ensure(c, c->rs_off, (size_t)m + 1, nomem)) return rc;
+    return ensure(c, c->rs_payload, (size_t)m * 6144, nomem);
 }
 
 // the tail of a chunk that v3r_encode has classed and packed: its codes, then its payload (once the size is known) go to the

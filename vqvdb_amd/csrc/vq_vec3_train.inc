@@ -61,21 +61,13 @@ V3TWs v3t_layout(unsigned char* base, int64_t leaves, int k_codes)
 
 size_t v3t_ws_bytes(int64_t leaves, int k_codes) { return leaves > 0 ? v3t_layout(nullptr, leaves, k_codes).bytes : 0; }
 
-int v3t_ensure_ws(vqhip_vec3_codec* c, int64_t m, hipStream_t s)
+int v3t_ensure_ws(vqhip_vec3_codec* c, int64_t m)
 {
     if (m <= c->tr_leaves) return VQHIP_OK;
-    if (c->tr_ws) {
-        HIPCHK(c, hipStreamSynchronize(s));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        hipFree(c->tr_ws);
-        c->tr_ws = nullptr;
-        c->tr_leaves = 0;
-    }
-    if (hipMalloc(&c->tr_ws, v3t_ws_bytes(m, c->k_codes)) != hipSuccess) {
-        (void)hipGetLastError();
-        c->tr_ws = nullptr;
+    if (int rc = ensure(c, c->tr_ws, v3t_ws_bytes(m, c->k_codes), [&](hipError_t) { return "vec3 training: cannot allocate the training workspace of " + std::to_string(m) + " leaves"; })) {
+        if (!c->tr_ws) c->tr_leaves = 0;   // (a failed synchronise leaves the old block and its layout)
         c->chunk_fitted = false;
-        return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 training: cannot allocate the training workspace of " + std::to_string(m) + " leaves");
+        return rc;
     }
     c->tr_leaves = m;
     return VQHIP_OK;
@@ -124,7 +116,7 @@ int v3t_forward(vqhip_vec3_codec* c, const float* leaves, int64_t n, float* stat
                 V3TWs& T, uint16_t** idx_used)
 {
     if (int rc = v3_ensure_ws(c, n)) return rc;
-    if (int rc = v3t_ensure_ws(c, n, s)) return rc;
+    if (int rc = v3t_ensure_ws(c, n)) return rc;
     T = v3t_layout(c->tr_ws, c->tr_leaves, c->k_codes);
     uint16_t* idx = idx_out ? idx_out : T.idx;
     float* flat = latent_out ? latent_out : T.flat;
@@ -152,15 +144,9 @@ int vqhip_vec3_train_begin(vqhip_vec3_codec* c, const float* cluster_size, const
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
     const size_t K = (size_t)c->k_codes;
-    if (!c->tr_cs) {
-        if (hipMalloc(&c->tr_cs, K * sizeof(float)) != hipSuccess || hipMalloc(&c->tr_avg, K * 64 * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->tr_cs) hipFree(c->tr_cs);
-            c->tr_cs = nullptr;
-            c->tr_avg = nullptr;
-            return v3_fail(c, VQHIP_ERR_NOMEM, "vec3 train_begin: cannot allocate the EMA buffers");
-        }
-    }
+    auto nomem = [](hipError_t) { return std::string("vec3 train_begin: cannot allocate the EMA buffers"); };
+    if (int rc = ensure(c, c->tr_cs, K, nomem)) return rc;
+    if (int rc = ensure(c, c->tr_avg, K * 64, nomem)) return rc;
     if (cluster_size) HIPCHK(c, hipMemcpy(c->tr_cs, cluster_size, K * sizeof(float), hipMemcpyHostToDevice));
     else {
         const std::vector<float> ones(K, 1.0f);
