@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import torch_ref_vec3 as tr  # noqa: E402
 import torch_ref_vec3_fulltrain as tf  # noqa: E402
 import torch_ref_vec3_train as trt  # noqa: E402
+from vec3_fulltrain_common import _screen, dev, forward, fwdbwd, new_codec, split  # noqa: E402
 from vqvdb_amd import synth_vec3, vec3_full_training, weightpack  # noqa: E402
 from vqvdb_amd.codec import HipVec3Codec  # noqa: E402
 
@@ -34,36 +35,6 @@ def W():
     return synth_vec3.make_weights(0)
 
 
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def new_codec(W):
-    c = HipVec3Codec(weightpack.dumps(W))
-    c.fulltrain_begin()
-    return c
-
-
-def fwdbwd(c, leaves, n_global=None, stream=0):
-    n = len(leaves)
-    x = dev(leaves)
-    g = torch.zeros(c.fulltrain_param_count(), dtype=torch.float32, device="cuda")
-    a = torch.zeros(c.fulltrain_aux_floats(), dtype=torch.float32, device="cuda")
-    c.fulltrain_fwdbwd_device(x.data_ptr(), n, n_global or n, g.data_ptr(), a.data_ptr(), stream=stream)
-    torch.cuda.synchronize()
-    return g.cpu().numpy(), a.cpu().numpy()
-
-
-def forward(c, leaves):
-    n = len(leaves)
-    x = dev(leaves)
-    idx = torch.zeros((n, 64), dtype=torch.int16, device="cuda")
-    rec = torch.zeros((n, 512, 3), dtype=torch.float32, device="cuda")
-    c.fulltrain_forward_device(x.data_ptr(), n, idx.data_ptr(), rec.data_ptr())
-    torch.cuda.synchronize()
-    return idx.cpu().numpy().view(np.uint16), rec.cpu().numpy()
-
-
 def gpu_steps(c, batches, lrs):
     """Steps of the device loop (fwdbwd + apply on one rank): per step the loss record (from aux) and the assignment."""
     recs = []
@@ -79,15 +50,6 @@ def gpu_steps(c, batches, lrs):
         r["idx"], r["grads"] = idx, g.cpu().numpy()
         recs.append(r)
     return recs
-
-
-def split(vec):
-    out, off = {}, 0
-    for name, shape in vec3_full_training.PARAM_SPECS:
-        size = int(np.prod(shape))
-        out[name] = vec[off:off + size]
-        off += size
-    return out
 
 
 def test_sizes(W):
@@ -126,37 +88,11 @@ def test_forward_consistency(W):
     c.close()
 
 
-def _screen(leaves, W, idx, n_keep=32):
-    """Indices of n_keep leaves whose ReLU inputs are all >= 2e-6 from zero and whose |recon - x| are all >= 1e-6 (fp64)."""
-    w = tr.weights_to_torch(W)
-    mins = []
-    orig = tr._gn_relu
-
-    def rec_gn(x, ww, prefix, eps=1e-5):
-        pre = torch.nn.functional.group_norm(x, 8, ww[prefix + ".weight"], ww[prefix + ".bias"], eps=eps)
-        mins.append(pre.abs().flatten(1).min(1).values)
-        return torch.relu(pre)
-
-    tr._gn_relu = rec_gn
-    try:
-        with torch.no_grad():
-            e = w["quantizer.embedding"]
-            out = tf.loss(leaves, w, e, torch.as_tensor(idx.reshape(-1).astype(np.int64)))
-    finally:
-        tr._gn_relu = orig
-    relu_min = torch.stack(mins).min(0).values.numpy()
-    x = np.asarray(leaves, np.float64).reshape(len(leaves), -1)
-    diff_min = np.abs(out["rec"].numpy().reshape(len(leaves), -1) - x).min(1)
-    ok = np.where((relu_min >= 2e-6) & (diff_min >= 1e-6))[0]
-    assert len(ok) >= n_keep, f"only {len(ok)} of {len(leaves)} leaves pass the screening"
-    return ok[:n_keep]
-
-
 def test_parameter_gradients_against_fp64_autograd(W):
     cand = synth_vec3.make_leaves(128, seed=9200)
     c = new_codec(W)
     idx, _ = forward(c, cand)
-    keep = _screen(cand, W, idx)
+    keep = _screen(cand, W, idx)[:32]
     leaves = np.ascontiguousarray(cand[keep])
     g, aux = fwdbwd(c, leaves)
     idx_b, _ = forward(c, leaves)

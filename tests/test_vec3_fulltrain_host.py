@@ -119,6 +119,32 @@ def test_losses_from_aux():
     assert abs(r["loss"] - (0.8 * 0.25 + 0.2 * 0.5 + 0.125)) < 1e-12 and r["perplexity"] == pytest.approx(1.0)
 
 
+def test_adamw_fp64_restatement_is_torch_adamw():
+    """tf.adamw_fp64 (the reference of the teacher-forced optimizer test on the GPU) against torch.optim.AdamW on float64
+    tensors: two steps, gradients over eight decades with exact zeros, to 1e-12 of |value| + |value before the step|."""
+    rng = np.random.default_rng(5)
+    n = 4099
+    hyper = dict(lr=1e-3, betas=(0.8, 0.99), eps=1e-6, weight_decay=0.01)
+    p = rng.standard_normal(n) * 0.1
+    grads = [rng.standard_normal(n) * 10.0 ** rng.uniform(-6, 2, n) for _ in range(2)]
+    grads[0][::17] = 0.0
+    grads[1][::5] = 0.0
+    tp = torch.tensor(p, dtype=torch.float64, requires_grad=True)
+    opt = torch.optim.AdamW([tp], **hyper)
+    m, v = np.zeros(n), np.zeros(n)
+    for step, g in enumerate(grads, 1):
+        before = (p, m, v)
+        p, m, v = tf.adamw_fp64(p, g, m, v, hyper["lr"], step, hyper["betas"], hyper["eps"], hyper["weight_decay"])
+        tp.grad = torch.tensor(g, dtype=torch.float64)
+        opt.step()
+        st = opt.state[tp]
+        assert int(st["step"]) == step
+        for name, mine, ref, old in (("p", p, tp.detach().numpy(), before[0]), ("m", m, st["exp_avg"].numpy(), before[1]),
+                                     ("v", v, st["exp_avg_sq"].numpy(), before[2])):
+            assert (np.abs(mine - ref) <= 1e-12 * (np.abs(ref) + np.abs(old))).all(), (step, name, np.abs(mine - ref).max())
+    assert np.abs(m).min() == 0.0 and np.abs(m).max() > 0.0      # elements whose gradient was zero in both steps are in
+
+
 @pytest.fixture(scope="module")
 def g():
     return np.load(GOLDEN)

@@ -102,6 +102,18 @@ def adamw_step(params: dict, grads: dict, state: dict, lr: float, step: int, bet
         p.addcdiv_(m, denom, value=-lr / (1 - b1 ** step))
 
 
+def adamw_fp64(p, g, m, v, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4) -> tuple:
+    """torch.optim.AdamW's update on flat arrays in numpy float64, functional -> (p, m, v).  Every argument enters with the
+    value it is given: hand in float32 arrays and np.float32 scalars to restate a float32 kernel's inputs."""
+    p, g, m, v = (np.asarray(a, np.float64) for a in (p, g, m, v))
+    lr, b1, b2, eps, wd = (float(a) for a in (lr, betas[0], betas[1], eps, weight_decay))
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    denom = np.sqrt(v) / math.sqrt(1.0 - b2 ** step) + eps
+    p = p * (1.0 - lr * wd) - (lr / (1.0 - b1 ** step)) * (m / denom)
+    return p, m, v
+
+
 def ema_update(st: dict, flat: torch.Tensor, idx: torch.Tensor, decay: float = 0.95, eps: float = 1e-4):
     """The EMA step of VectorQuantizerEMA (VQVAE_v2.py:135-144) with a given assignment; updates st in place."""
     k = st["embedding"].shape[0]
