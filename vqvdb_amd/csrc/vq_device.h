@@ -69,6 +69,10 @@ __device__ __forceinline__ void buf_st16(f32x4 v, vq_buf b, unsigned lane_bytes,
 {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), b, (int)(lane_bytes + uniform_bytes), 0, 0);
 }
+__device__ __forceinline__ void buf_st4(float v, vq_buf b, unsigned lane_bytes, unsigned uniform_bytes)
+{
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), b, (int)(lane_bytes + uniform_bytes), 0, 0);
+}
 // streaming (non-temporal) store: the output is read next by another kernel, from HBM anyway
 __device__ __forceinline__ void buf_st16_nt(f32x4 v, vq_buf b, unsigned lane_bytes, unsigned uniform_bytes)
 {

@@ -33,6 +33,7 @@
 #include "vq_stem_taps.h"
 #include "vq_conv4_lds.h"
 #include "vq_first_roll.h"
+#include "vq_first_once.h"
 #include "vq_convdown_lds.h"
 #include "vq_train_kernels.h"
 #include "vq_grad_kernels.h"
@@ -147,6 +148,7 @@ const std::map<std::string, KernelInfo>& kernel_info()
     static const std::map<std::string, KernelInfo> m = {
         {"enc_conv_first_stats", {0.0, 2.0 * 221184 * 0.7703}},   // recomputation: the op is counted once, on the second pass
         {"enc_conv_first_gn", {2.0 * 221184, 2.0 * 221184 * 0.7703}},
+        {"enc_conv_first", {2.0 * 221184, 264.0 * 2048}},   // conv_first_once_k: 264 16x16x4 MFMAs per leaf (kd skipped at the border planes, kh issued in full)
         {"enc_res16_conv1", {2.0 * 3538944, 2.0 * 3538944 * 0.7703}},
         {"enc_res16_conv2", {2.0 * 3538944, 2.0 * 3538944 * 0.7703}},
         {"enc_down", {2.0 * 2097152, 2.0 * 2097152 * 0.669922}},
@@ -192,6 +194,7 @@ struct vqhip_codec {
     bool conv8_w16 = true;   // ... with 16 waves (one half row each; a half row is a statistics block); VQHIP_CONV8=w8 selects 8 (one row each)
     bool convdown_lds = true;   // down conv of large passes: input planes streamed through LDS once, weights from L1 / L2 (vq_convdown_lds.h); VQHIP_DOWN=rows selects the row kernel (input re-fetched 3.06x)
     bool conv4_lds = true;   // 32-channel 4^3 convs of large passes: input planes in an LDS ring, weights straight from L1 / L2 (vq_conv4_lds.h); VQHIP_CONV4=rows selects the row kernel (weights LDS-resident, every input row re-fetched 6.25x)
+    bool first_once = true;  // first conv of full chunks issued once, an 8-leaf group's output held in the accumulators of one workgroup (conv_first_once_k, vq_first_once.h); VQHIP_FIRST=twopass|steps|roll0 and VQHIP_FIRST_SRC=raw select the two-pass sequence below
     bool first_roll_stats = false;   // ... for the statistics pass too (VQHIP_FIRST=roll0; measured slower)
     bool first_raw = false;  // VQHIP_FIRST_SRC=raw: the first conv reads the caller's float[leaf][512] layout itself and pack_leaves_k is not launched (round 6; measured SLOWER: 0.425 + 0.465 ms against 0.069 + 0.322 + 0.396 ms with the row layout — 16 cache lines per load instead of 6)
     const float* cur_leaves = nullptr;   // the current pass's input leaves (device), for the split path's first conv
@@ -1274,7 +1277,14 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
     c->cur_leaves = raw ? d_leaves : nullptr;
     if (!raw || xt) L.run("pack_leaves", [&] { hipLaunchKernelGGL(pack_leaves_k, dim3(nt, nt <= 128 ? 8 : 1), dim3(256), 0, s, d_leaves, a["xr"], xt, n); });
     if (use_split(c, nt, false)) return encode_chunk_split(c, L, n, d_idx, s, d_latent);
-    {
+    if (c->first_once && !c->first_raw && !c->training && !c->full_training) {
+        // first conv once: conv + GroupNorm(4,16) + ReLU + statistics for res.gn1 out of the accumulators of a workgroup per 8-leaf group
+        ConvArgs A{};
+        A.in = a["xr"], A.out = a["e_a1"], A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"], A.in_gamma = w["eg0.w"], A.in_beta = w["eg0.b"];
+        A.out_mean = S.a1m, A.out_rstd = S.a1r, A.n_tiles = nt;
+        float* y1 = (c->debug || c->keep_y1) ? a["e_y1"] : nullptr;
+        L.run("enc_conv_first", [&] { hipLaunchKernelGGL(conv_first_once_k, dim3(std::min(4 * nt, c->n_cus)), dim3(512), 0, s, A, y1, S.y1m, S.y1r); });
+    } else {
         // first conv twice: statistics pass, then recompute + GroupNorm(4,16) + ReLU + statistics for res.gn1
         ConvArgs A{};
         A.in = raw ? d_leaves : a["xr"], A.out = (c->debug || c->keep_y1) ? a["e_y1"] : nullptr, A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"];
@@ -1842,7 +1852,10 @@ int vqhip_create(const char* pack_path, const void* pack_bytes, size_t pack_size
     if (const char* e = std::getenv("VQHIP_DOWN")) c->convdown_lds = std::strcmp(e, "rows") != 0;
     if (const char* e = std::getenv("VQHIP_CONV4")) c->conv4_lds = std::strcmp(e, "rows") != 0;
     if (const char* e = std::getenv("VQHIP_FIRST_SRC")) c->first_raw = std::strcmp(e, "raw") == 0;
-    if (const char* e = std::getenv("VQHIP_FIRST")) c->first_roll = std::strcmp(e, "steps") != 0, c->first_roll_stats = std::strcmp(e, "roll0") == 0;
+    if (const char* e = std::getenv("VQHIP_FIRST")) {   // twopass | steps | roll0: the two-pass sequence (with its default kernels / conv_first_k for both passes / the row window for both)
+        c->first_once = std::strcmp(e, "twopass") != 0 && std::strcmp(e, "steps") != 0 && std::strcmp(e, "roll0") != 0;
+        c->first_roll = std::strcmp(e, "steps") != 0, c->first_roll_stats = std::strcmp(e, "roll0") == 0;
+    }
     if (const char* e = std::getenv("VQHIP_CONV8")) c->conv8_lds = std::strcmp(e, "rows") != 0, c->conv8_w16 = std::strcmp(e, "w8") != 0;
     if (const char* e = std::getenv("VQHIP_TAIL16_TILES")) c->tail16_tiles = std::atoi(e);
     if (const char* e = std::getenv("VQHIP_HOST_SPLIT")) {
