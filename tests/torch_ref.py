@@ -61,20 +61,23 @@ def decoder(q, w, tape=None):
     return torch.sigmoid(pre)
 
 
-def quantize(z, codebook, commitment_cost=0.25):
-    """Assignment with the expanded distance, straight-through output, commitment loss (VQVAE_v2.py:107-150); no EMA here."""
-    flat = z.permute(0, 2, 3, 4, 1).reshape(-1, z.shape[1])
-    d = (flat ** 2).sum(1, keepdim=True) + (codebook ** 2).sum(1) - 2 * flat @ codebook.t()
-    idx = d.argmin(1)
+def quantize(z, codebook, commitment_cost=0.25, idx=None):
+    """Assignment with the expanded distance, straight-through output, commitment loss (VQVAE_v2.py:107-150); no EMA here.
+    idx (int64 [B*64], row = leaf * 64 + position) forces the assignment instead of the argmin."""
+    if idx is None:
+        flat = z.permute(0, 2, 3, 4, 1).reshape(-1, z.shape[1])
+        d = (flat ** 2).sum(1, keepdim=True) + (codebook ** 2).sum(1) - 2 * flat @ codebook.t()
+        idx = d.argmin(1)
     q = codebook[idx].view(z.shape[0], *z.shape[2:], z.shape[1]).permute(0, 4, 1, 2, 3)
     loss = commitment_cost * F.mse_loss(z, q.detach())
     return z + (q - z).detach(), loss, idx
 
 
-def training_loss(x, w, commitment_cost=0.25, mse_weight=0.8, l1_weight=0.2, tape=None):
-    """Forward of one training step: returns (loss, dict of pieces).  x: [B,1,8,8,8].  tape: dict receiving intermediates."""
+def training_loss(x, w, commitment_cost=0.25, mse_weight=0.8, l1_weight=0.2, tape=None, idx=None):
+    """Forward of one training step: returns (loss, dict of pieces).  x: [B,1,8,8,8].  tape: dict receiving intermediates.
+    idx: a forced code assignment (see quantize)."""
     z = _rec(tape, "z", encoder(x, w, tape))
-    q, vq_loss, idx = quantize(z, w["quantizer.embedding"], commitment_cost)
+    q, vq_loss, idx = quantize(z, w["quantizer.embedding"], commitment_cost, idx)
     q = _rec(tape, "q", q)
     recon = decoder(q, w, tape)
     mse, l1 = F.mse_loss(recon, x), F.l1_loss(recon, x)
