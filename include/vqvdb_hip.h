@@ -176,6 +176,12 @@ int vqhip_reserve(vqhip_codec* codec, int64_t n_leaves);
  * chunk size in effect (it may have been halved to fit a shared GPU's free memory). */
 int64_t vqhip_workspace_bytes(const vqhip_codec* codec);
 int64_t vqhip_chunk_leaves(const vqhip_codec* codec);
+/* Compute units: *device is the device's own count, *in_use the count the persistent-workgroup grids, the weight-gradient
+ * slices and the launch policies are derived from.  They differ only under VQHIP_CUS=k (1 <= k <= *device, read at create;
+ * anything else makes vqhip_create fail with VQHIP_ERR_INVALID): the launch geometry of a device with k compute units, for
+ * tests and for parts that report fewer.  It takes no compute unit away from the device and results never depend on it (the weight
+ * gradients' order of partial sums does).  Either pointer may be NULL. */
+int vqhip_compute_units(const vqhip_codec* codec, int* device, int* in_use);
 
 /* ---- codebook training (extension; SURVEY.md §8 f-2, stage 1) ----------------------------------------------
  * The training-mode forward of VectorQuantizerEMA (python/VQVAE_v2.py:107-156) on the encoder's outputs: assign

@@ -22,8 +22,8 @@ from vqvdb_amd import codec, synth_vec3  # noqa: E402
 
 HEADER = os.path.join(ROOT, "include", "vqvdb_hip_vec3_bounded.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_vec3_v1.npz")
-# include/vqvdb_hip.h as it was before this header existed: its Vec3 name list is fixed
-VQVDB_HIP_H_SHA256 = "586055777d65215ceb3c6ad4876c4e4e325693ec068254e1ea1727b6066587b0"
+# include/vqvdb_hip.h as it was before this header existed, plus vqhip_compute_units on the scalar handle: its Vec3 name list is fixed
+VQVDB_HIP_H_SHA256 = "9830c05c5b19e6485c33269ae73b1adf9861b720a6d076e56c4d6801afd33551"
 NAMES = ["vqhip_vec3_roundtrip_device", "vqhip_vec3_select_outliers_device", "vqhip_vec3_compress_bounded"]
 
 

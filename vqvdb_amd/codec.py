@@ -97,6 +97,7 @@ ABI_SYMBOLS = [
     "vqhip_fulltrain_begin", "vqhip_fulltrain_param_count", "vqhip_fulltrain_forward_device", "vqhip_fulltrain_fwdbwd_device",
     "vqhip_fulltrain_apply_device", "vqhip_fulltrain_get_params", "vqhip_fulltrain_set_params",
     "vqhip_fulltrain_get_opt_state", "vqhip_fulltrain_set_opt_state", "vqhip_workspace_bytes", "vqhip_chunk_leaves", "vqhip_multi_worker_info", "vqhip_fulltrain_fwdbwd_overlap_device", "vqhip_fulltrain_decoder_offset", "vqhip_fulltrain_ready_stream", "vqhip_fulltrain_set_folded_tail",
+    "vqhip_compute_units",
     "vqhip_vec3_create", "vqhip_vec3_destroy", "vqhip_vec3_last_error", "vqhip_vec3_model_info", "vqhip_vec3_encode", "vqhip_vec3_decode",
     "vqhip_vec3_encode_device", "vqhip_vec3_decode_device", "vqhip_vec3_set_chunk_leaves", "vqhip_vec3_chunk_leaves",
     "vqhip_vec3_debug_enable", "vqhip_vec3_debug_fetch",
@@ -246,6 +247,7 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_workspace_bytes.restype = ctypes.c_int64
     lib.vqhip_chunk_leaves.argtypes = [vp]
     lib.vqhip_chunk_leaves.restype = ctypes.c_int64
+    lib.vqhip_compute_units.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci)]
     lib.vqhip_fulltrain_get_opt_state.argtypes = [vp, vp, vp]
     lib.vqhip_fulltrain_set_opt_state.argtypes = [vp, vp, vp]
     lib.vqhip_profile_enable.argtypes = [vp, ci]
@@ -1513,6 +1515,12 @@ class HipCodec:
 
     def chunk_leaves(self) -> int:
         return int(self._lib.vqhip_chunk_leaves(self._h))
+
+    def compute_units(self) -> tuple:
+        """(the device's compute units, the count the launch geometry is derived from): equal unless VQHIP_CUS was set at create."""
+        device, in_use = ctypes.c_int(), ctypes.c_int()
+        self._check(self._lib.vqhip_compute_units(self._h, ctypes.byref(device), ctypes.byref(in_use)))
+        return device.value, in_use.value
 
     def reserve(self, n: int):
         self._check(self._lib.vqhip_reserve(self._h, n))

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
 #include <cstdlib>
 #include <memory>
 #include <atomic>
@@ -180,7 +181,8 @@ struct vqhip_codec {
     std::string err;
     hipStream_t stream = nullptr;
     int64_t chunk = 65536;
-    int n_cus = 256;         // compute units of the device (persistent-workgroup launches)
+    int n_cus = 256;         // compute units the persistent-workgroup launches, the weight-gradient slices and the launch policies count on: the device's, or fewer (VQHIP_CUS)
+    int n_cus_device = 256;  // compute units of the device itself (CU mask of the reduction stream)
     bool stem_fused = true;  // decoder front of large passes: one kernel; VQHIP_STEM=split selects stem_lut_k + gn_relu_stats_k
     bool stem_taps = true;   // ... the (tap, code) table streamed through an LDS ring tap by tap (stem_taps_k, vq_stem_taps.h: 0.81 -> 0.57 ms); VQHIP_STEM=gather selects stem_fused_k (gather through the L1)
     bool tail_groups = false; // ... VQHIP_TAIL=groups: the output planes in three groups instead of five units, every input plane read 2.5x instead of 3.5x (tail_groups16_k, vq_tail_groups.h; measured equal in time, 33 spilled registers)
@@ -1848,7 +1850,17 @@ int vqhip_create(const char* pack_path, const void* pack_bytes, size_t pack_size
         c->err = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
         return bail(VQHIP_ERR_DEVICE);
     }
-    c->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    c->n_cus = c->n_cus_device = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    if (const char* e = std::getenv("VQHIP_CUS")) {   // launch geometry as on a device with fewer compute units; masks no compute unit off
+        char* end = nullptr;
+        errno = 0;
+        const long k = std::strtol(e, &end, 10);
+        if (!*e || *end || errno || k < 1 || k > c->n_cus_device) {
+            c->err = std::string("VQHIP_CUS=") + e + ": not an integer in [1, " + std::to_string(c->n_cus_device) + "] (the device's compute units)";
+            return bail(VQHIP_ERR_INVALID);
+        }
+        c->n_cus = (int)k;
+    }
     if (const char* e = std::getenv("VQHIP_DOWN")) c->convdown_lds = std::strcmp(e, "rows") != 0;
     if (const char* e = std::getenv("VQHIP_CONV4")) c->conv4_lds = std::strcmp(e, "rows") != 0;
     if (const char* e = std::getenv("VQHIP_FIRST_SRC")) c->first_raw = std::strcmp(e, "raw") == 0;
@@ -1961,6 +1973,14 @@ int vqhip_reserve(vqhip_codec* c, int64_t n)
 int64_t vqhip_workspace_bytes(const vqhip_codec* c) { return c ? (int64_t)c->ws.bytes() : -1; }
 
 int64_t vqhip_chunk_leaves(const vqhip_codec* c) { return c ? c->chunk : -1; }
+
+int vqhip_compute_units(const vqhip_codec* c, int* device, int* in_use)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (device) *device = c->n_cus_device;
+    if (in_use) *in_use = c->n_cus;
+    return VQHIP_OK;
+}
 
 int vqhip_encode_device(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_idx, void* stream)
 {

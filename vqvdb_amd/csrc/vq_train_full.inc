@@ -275,8 +275,8 @@ int side_stream(vqhip_codec* c, hipStream_t s, hipStream_t& ws)
         if (qe && std::strcmp(qe, "prio") == 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
             HIPCHK(c, hipStreamCreateWithPriority(&c->ft_red, hipStreamNonBlocking, hi));
         } else {
-            std::vector<uint32_t> mask((size_t)(c->n_cus + 31) / 32, 0xffffffffu);
-            if (c->n_cus % 32) mask.back() = (1u << (c->n_cus % 32)) - 1u;
+            std::vector<uint32_t> mask((size_t)(c->n_cus_device + 31) / 32, 0xffffffffu);   // the device's own count: VQHIP_CUS masks nothing off
+            if (c->n_cus_device % 32) mask.back() = (1u << (c->n_cus_device % 32)) - 1u;
             if (hipExtStreamCreateWithCUMask(&c->ft_red, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
                 (void)hipGetLastError();
                 HIPCHK(c, hipStreamCreateWithFlags(&c->ft_red, hipStreamNonBlocking));
@@ -632,7 +632,7 @@ struct Bwd {
                 constexpr int NT4 = rows4_threads<CIN, COUT>();
                 // (train_wgrad_cu_pct < 100: fewer slices than CUs, so that the data-gradient chain's kernels — whose LDS does not fit beside a
                 // weight-gradient workgroup on one CU — always find free CUs)
-                const int Q = (int)std::min<int64_t>((int64_t)100 * nt, (int64_t)(c->n_cus * c->train_wgrad_cu_pct / 100) * (NT4 >= 512 ? 1 : CIN == 32 && COUT == 32 ? 4 : 2));
+                const int Q = (int)std::min<int64_t>((int64_t)100 * nt, std::max<int64_t>(1, c->n_cus * c->train_wgrad_cu_pct / 100) * (NT4 >= 512 ? 1 : CIN == 32 && COUT == 32 ? 4 : 2));
                 static_assert((size_t)(512 + 8) * 3 * COUT * CIN <= (size_t)WG_GROUPS * WG_MAX || NT4 >= 512, "partial buffer");
                 static_assert((size_t)(256 + 8) * 3 * COUT * CIN <= (size_t)WG_GROUPS * WG_MAX, "partial buffer");
                 if ((size_t)(Q + 8) * 3 * COUT * CIN <= (size_t)WG_GROUPS * WG_MAX) {
