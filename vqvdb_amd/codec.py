@@ -119,6 +119,9 @@ VEC3_FULLTRAIN_SYMBOLS = [
 # every symbol include/vqvdb_hip_vec3_precision.h declares (Vec3 inference precision mode; kept apart from the lists above)
 VEC3_PRECISION_SYMBOLS = ["vqhip_vec3_set_precision", "vqhip_vec3_get_precision"]
 VEC3_PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_VEC3_PRECISION_*
+# every symbol include/vqvdb_hip_precision.h declares (decode precision mode of the scalar handle; kept apart from the lists above)
+PRECISION_SYMBOLS = ["vqhip_set_decode_mode", "vqhip_get_decode_mode"]
+PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_PRECISION_*
 # every symbol include/vqvdb_hip_vec3_bounded.h declares (Vec3 error-bounded round trip; kept apart from the lists above)
 VEC3_BOUNDED_SYMBOLS = ["vqhip_vec3_roundtrip_device", "vqhip_vec3_select_outliers_device", "vqhip_vec3_compress_bounded"]
 VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
@@ -305,6 +308,11 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_set_precision.argtypes = [vp, ci]
     lib.vqhip_vec3_get_precision.argtypes = [vp, vp]
     for name in VEC3_PRECISION_SYMBOLS:
+        getattr(lib, name).restype = ci
+    # include/vqvdb_hip_precision.h
+    lib.vqhip_set_decode_mode.argtypes = [vp, ci]
+    lib.vqhip_get_decode_mode.argtypes = [vp, vp]
+    for name in PRECISION_SYMBOLS:
         getattr(lib, name).restype = ci
     # include/vqvdb_hip_vec3_bounded.h
     lib.vqhip_vec3_roundtrip_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -944,7 +952,8 @@ class HipVec3Codec:
 class HipCodec:
     """Thin owner of a ``vqhip_codec*`` — the C ABI one-to-one, numpy/raw pointers in and out."""
 
-    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0):
+    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0, decode_precision: str = "fp32"):
+        self.check_decode_precision(decode_precision)
         self._lib = load_library()
         self._h = ctypes.c_void_p()
         if isinstance(pack, (bytes, bytearray, memoryview)):
@@ -954,6 +963,28 @@ class HipCodec:
             rc = self._lib.vqhip_create(os.fspath(pack).encode(), None, 0, device_id, ctypes.byref(self._h))
         if rc != 0:
             raise RuntimeError(self._lib.vqhip_last_error(None).decode())
+        if decode_precision != "fp32":
+            self.decode_precision = decode_precision
+
+    @staticmethod
+    def check_decode_precision(precision) -> int:
+        """"fp32" / "bf16" -> VQHIP_PRECISION_* (include/vqvdb_hip_precision.h)."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"decode_precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
+        return PRECISIONS[precision]
+
+    @property
+    def decode_precision(self) -> str:
+        """Operand precision of the decoder's two 64-channel convs in decode / decode_device / decode_leaves / decompress_file and
+        the debug_fetch after them: "fp32" (default) or "bf16" (DESIGN §23).  Every bounded, residual, rate, round-trip and
+        training call decodes in fp32 whatever this says."""
+        mode = ctypes.c_int(-1)
+        self._check(self._lib.vqhip_get_decode_mode(self._h, ctypes.byref(mode)))
+        return {v: k for k, v in PRECISIONS.items()}[mode.value]
+
+    @decode_precision.setter
+    def decode_precision(self, precision: str):
+        self._check(self._lib.vqhip_set_decode_mode(self._h, self.check_decode_precision(precision)))
 
     def _check(self, rc: int):
         if rc != 0:
@@ -1204,7 +1235,11 @@ class HipCodec:
         if isinstance(leaves, np.ndarray):
             leaves = self.check_leaves(leaves)
             idx, err, _ = self._compress_bounded_host(leaves, float("inf"))
-            return (idx, err, self.decode(idx)) if return_recon else (idx, err)
+            if not return_recon:
+                return idx, err
+            # the reconstruction the errors were measured against: the fp32 decoder whatever decode_precision says (the bounded
+            # decompress with no outliers is that decode)
+            return idx, err, self._decompress_bounded_host(idx, np.empty(0, np.int64), np.empty((0, LEAF_VOXELS), np.float32))
         import torch
         if not (isinstance(leaves, torch.Tensor) and leaves.is_cuda and leaves.dtype == torch.float32 and leaves.is_contiguous()):
             raise TypeError("leaves must be a float32 numpy array or a contiguous float32 torch tensor on the GPU")

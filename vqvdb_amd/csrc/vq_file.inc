@@ -187,7 +187,9 @@ int decompress_file_impl(vqhip_codec* c, const char* path, const char* residual_
                 cv.notify_all();
                 return rrc;
             },
-            &stage);
+            &stage,
+            // the plain decompress follows the handle's decode mode; a sidecar's records are corrections of the fp32 reconstruction
+            residual_path ? VQHIP_PRECISION_FP32 : c->decode_precision);
         {
             std::lock_guard<std::mutex> lk(mu);
             stop = true;

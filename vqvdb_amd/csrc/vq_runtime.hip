@@ -28,6 +28,7 @@
 #include "../../include/vqvdb_hip.h"
 #include "../../include/vqvdb_hip_bounded.h"
 #include "../../include/vqvdb_hip_residual.h"
+#include "../../include/vqvdb_hip_precision.h"
 #include "vq_buffers.h"
 #include "vq_kernels.h"
 #include "vq_conv8_lds.h"
@@ -41,6 +42,7 @@
 #include "vq_train_tail.h"
 #include "vq_tail_rows.h"
 #include "vq_tail_groups.h"
+#include "vq_dec64_bf16.h"
 
 namespace {
 
@@ -160,6 +162,8 @@ const std::map<std::string, KernelInfo>& kernel_info()
         {"dec_stem_gn", {0.0, 0.0}},  // table lookups: the 14.2 M MAC/leaf of the reference op are not executed (stem_lut_k)
         {"dec_res64_conv1", {2.0 * 7077888, 2.0 * 7077888 * 0.578704}},
         {"dec_res64_conv2", {2.0 * 7077888, 2.0 * 7077888 * 0.578704}},
+        {"dec_res64_conv1_bf16", {2.0 * 7077888, 2.0 * 7077888 * 0.578704}},   // bf16 decode mode (vq_dec64_bf16.h): the same taps on the bf16 MFMA
+        {"dec_res64_conv2_bf16", {2.0 * 7077888, 2.0 * 7077888 * 0.578704}},
         // folded up_conv+pixshuf+final: nominal = the reference ops' dense count; "effective" = the MACs the
         // folded map really needs (884 736/leaf); the kernel issues (160 steps x 4 + 64 steps x 2 cout tiles) x 32 voxels x 64
         // channels = 1 572 864 MAC/leaf (round 3: the MFMAs of a voxel plane against input planes it cannot depend on are skipped;
@@ -287,6 +291,11 @@ struct vqhip_codec {
     int64_t rs_pin_leaves = 0;         // ... whose sections are positioned for this many leaves
     // size sweep (vq_rate.inc): the histogram [64][19] of the host calls
     DevBuf<int64_t> rate_hist;
+    // bf16 decode mode (vqvdb_hip_precision.h): the mode of the plain decode calls, the bf16 A fragments of the two 64 -> 64
+    // convs (grown at the first switch), and whether the fp32 fragments they are packed from have changed since (training)
+    int decode_precision = VQHIP_PRECISION_FP32;
+    DevBuf<uint16_t> bf_r64c1, bf_r64c2;
+    bool bf_stale = true;
 };
 
 namespace {
@@ -1378,8 +1387,50 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
     return L.rc;
 }
 
+// ---- bf16 decode mode (vqvdb_hip_precision.h; kernels in vq_dec64_bf16.h) ----
+// The bf16 A fragments of the two convs, packed on the device from the live fp32 fragments ("r64c1.w16", "r64c2.w16": uploaded at
+// create, rebuilt by refrag_all after every training update, which marks these stale).  Buffers first, so that a failed allocation
+// leaves the handle as it was.  The pack is followed by a wait: it happens once per weight change, and a later call may use
+// another stream.
+int ensure_bf16_frags(vqhip_codec* c, hipStream_t s)
+{
+    if (!c->bf_stale && c->bf_r64c1 && c->bf_r64c2) return VQHIP_OK;
+    int rc;
+    if ((rc = ensure(c, c->bf_r64c1, (size_t)d64b::FRAG_ELEMS, "the bf16 fragments of decoder.res_stack.0.conv1"))) return rc;
+    if ((rc = ensure(c, c->bf_r64c2, (size_t)d64b::FRAG_ELEMS, "the bf16 fragments of decoder.res_stack.0.conv2"))) return rc;
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(d64b::conv_k<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d64b::LDS_BYTES));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(d64b::conv_k<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d64b::LDS_BYTES));
+    constexpr int wgs = (d64b::FRAG_ELEMS / 8 + 255) / 256;
+    hipLaunchKernelGGL(d64b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r64c1.w16"], c->bf_r64c1.get());
+    hipLaunchKernelGGL(d64b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r64c2.w16"], c->bf_r64c2.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->bf_stale = false;
+    return VQHIP_OK;
+}
+
+// d_d2 (+ its statistics in st_b) -> d_y4 -> d_x6 with the statistics the tail needs, for any number of tiles: ONE kernel per conv
+// whatever the batch size, so a leaf's bits do not depend on the launch path.  Each conv stores per-block partials and the combine
+// kernels of the position-split path finish them (gn2 statistics into st_a; channel sums and attention gates).
+void launch_dec64_bf16(vqhip_codec* c, Launcher& L, int nt, hipStream_t s)
+{
+    auto& a = c->act;
+    auto& w = c->dw;
+    d64b::Args B{};
+    B.in = a["d_d2"], B.out = a["d_y4"], B.wf = c->bf_r64c1, B.bias = w["r64c1.braw"];
+    B.in_mean = a["st_b.mean"], B.in_rstd = a["st_b.rstd"], B.in_gamma = w["r64g1.w"], B.in_beta = w["r64g1.b"];
+    B.part_s = reinterpret_cast<double*>(a["part_s"]), B.part_q = reinterpret_cast<double*>(a["part_q"]);
+    L.run("dec_res64_conv1_bf16", [&] { hipLaunchKernelGGL(d64b::conv_k<false>, dim3(2 * nt), dim3(d64b::THREADS), d64b::LDS_BYTES, s, B); });
+    L.run("dec_stats_y4", [&] { hipLaunchKernelGGL(gn_combine_k<true>, dim3(nt), dim3(512), 0, s, B.part_s, B.part_q, a["st_a.mean"], a["st_a.rstd"], 8, 1.0 / 512.0); });
+    B.in = a["d_y4"], B.out = a["d_x6"], B.wf = c->bf_r64c2, B.bias = w["r64c2.braw"], B.skip = a["d_d2"];
+    B.in_mean = a["st_a.mean"], B.in_rstd = a["st_a.rstd"], B.in_gamma = w["r64g2.w"], B.in_beta = w["r64g2.b"];
+    B.part_s = nullptr, B.part_q = nullptr, B.part_c = a["part_c"];
+    L.run("dec_res64_conv2_bf16", [&] { hipLaunchKernelGGL(d64b::conv_k<true>, dim3(2 * nt), dim3(d64b::THREADS), d64b::LDS_BYTES, s, B); });
+    L.run("dec_csum_x6", [&] { hipLaunchKernelGGL((csum_combine_k<64>), dim3(nt), dim3(512), 0, s, a["part_c"], a["csum"], w["dfc0"], w["dfc2"], a["gate"]); });
+}
+
 // position-split decode for small batches (see encode_chunk_split)
-int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_t n, float* d_out, hipStream_t s)
+int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_t n, float* d_out, hipStream_t s, int precision)
 {
     const int nt = (int)((n + 31) / 32);
     auto& a = c->act;
@@ -1427,7 +1478,9 @@ int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_
         }
         combine64("dec_stats_d2", a["st_b.mean"], a["st_b.rstd"]);
     }
-    {
+    if (precision == VQHIP_PRECISION_BF16) {
+        launch_dec64_bf16(c, L, nt, s);
+    } else {
         ConvArgs A{};
         A.in = a["d_d2"], A.out = a["d_y4"], A.wfrag = w["r64c1.w"], A.bias_frag = w["r64c1.b"];
         A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"], A.n_tiles = nt;
@@ -1471,7 +1524,9 @@ int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_
     return L.rc;
 }
 
-int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, hipStream_t s)
+// precision: VQHIP_PRECISION_* of the two 64 -> 64 convs.  Only the plain decode entry points pass the handle's mode; every call that
+// states or checks an error bound (bounded, residual, rate, round trip), training and vqhip_multi_* take the default.
+int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, hipStream_t s, int precision = VQHIP_PRECISION_FP32)
 {
     int rc = ensure_workspace(c, n);
     if (rc) return rc;
@@ -1481,7 +1536,8 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
     Launcher L{c, s, n};
     const int g4 = (nt + 3) / 4, g8 = (nt + 7) / 8;
 
-    if (use_split(c, nt, true)) return decode_chunk_split(c, L, d_idx, n, d_out, s);
+    if (precision == VQHIP_PRECISION_BF16 && (rc = ensure_bf16_frags(c, s))) return rc;
+    if (use_split(c, nt, true)) return decode_chunk_split(c, L, d_idx, n, d_out, s, precision);
     if (c->stem_fused) {   // gather + stem + GroupNorm + ReLU + statistics in one kernel: the stem output stays in LDS
         StemFusedArgs F{};
         F.idx = d_idx, F.T = w["ds.lut"], F.bias = w["ds.b"], F.gamma = w["dg0.w"], F.beta = w["dg0.b"], F.d2 = a["d_d2"];
@@ -1502,21 +1558,25 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
             L.run("dec_gn_relu_stats", [&] { hipLaunchKernelGGL((gn_relu_stats_k<64, 64, 8>), dim3(g4), dim3(256), 0, s, A); });
         }
     }
-    {
-        ConvArgs A{};
-        A.in = a["d_d2"], A.out = a["d_y4"], A.wfrag = w["r64c1.w"], A.bias_frag = w["r64c1.b"];
-        A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"];
-        A.out_mean = a["st_a.mean"], A.out_rstd = a["st_a.rstd"], A.n_tiles = nt;
-        A.wfrag = w["r64c1.w16"], A.bias_frag = w["r64c1.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-        L.run("dec_res64_conv1", [&] { hipLaunchKernelGGL(k_dec_r64c1_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]); });
-    }
-    {
-        ConvArgs A{};
-        A.in = a["d_y4"], A.out = a["d_x6"], A.wfrag = w["r64c2.w"], A.bias_frag = w["r64c2.b"], A.skip = a["d_d2"];
-        A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
-        A.out_csum = a["csum"], A.n_tiles = nt;
-        A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-        L.run("dec_res64_conv2", [&] { hipLaunchKernelGGL(k_dec_r64c2_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+    if (precision == VQHIP_PRECISION_BF16) {
+        launch_dec64_bf16(c, L, nt, s);
+    } else {
+        {
+            ConvArgs A{};
+            A.in = a["d_d2"], A.out = a["d_y4"], A.wfrag = w["r64c1.w"], A.bias_frag = w["r64c1.b"];
+            A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"];
+            A.out_mean = a["st_a.mean"], A.out_rstd = a["st_a.rstd"], A.n_tiles = nt;
+            A.wfrag = w["r64c1.w16"], A.bias_frag = w["r64c1.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
+            L.run("dec_res64_conv1", [&] { hipLaunchKernelGGL(k_dec_r64c1_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+        }
+        {
+            ConvArgs A{};
+            A.in = a["d_y4"], A.out = a["d_x6"], A.wfrag = w["r64c2.w"], A.bias_frag = w["r64c2.b"], A.skip = a["d_d2"];
+            A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
+            A.out_csum = a["csum"], A.n_tiles = nt;
+            A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
+            L.run("dec_res64_conv2", [&] { hipLaunchKernelGGL(k_dec_r64c2_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+        }
     }
     {
         ConvArgs A{};
@@ -1629,6 +1689,7 @@ int refresh_tables(vqhip_codec* c)
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->tables_stale = false;
+    c->bf_stale = true;   // every table that follows the live parameters is rebuilt after a training update, the bf16 decode mode's at its next call
     return VQHIP_OK;
 }
 
@@ -1661,7 +1722,7 @@ struct PipeStage {   // empty members are skipped
 };
 
 int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool want_stage, const ProduceFn& produce, const ConsumeFn& consume,
-                 const PipeStage* stage = nullptr)
+                 const PipeStage* stage = nullptr, int decode_precision = VQHIP_PRECISION_FP32)
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->chunk_fitted) fit_chunk_to_free_memory(c), c->chunk_fitted = true;
@@ -1682,7 +1743,7 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
     // what every chunk gets, in either arrangement below: its kernels on the compute stream ...
     auto chunk_work = [&](int64_t o, int64_t m, int slot) -> int {
         int r = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream)
-                          : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream);
+                          : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream, decode_precision);
         if (!r && stage && stage->device) r = stage->device(o, m, slot, c->stream);
         return r;
     };
@@ -1779,7 +1840,7 @@ void scatter_leaves(float* const* dst, const float* src, int64_t m)
 
 // contiguous blocks or leaf-pointer arrays (vqhip_encode / _decode / _encode_leaves / _decode_leaves)
 int run_host_pipeline(vqhip_codec* c, bool is_encode, const void* in, void* out, int64_t n, const float* const* in_ptrs = nullptr,
-                      float* const* out_ptrs = nullptr)
+                      float* const* out_ptrs = nullptr, int decode_precision = VQHIP_PRECISION_FP32)
 {
     const size_t in_b = is_encode ? 2048 : 64, out_b = is_encode ? 64 : 2048;
     // leaf blocks go through pinned staging (copied by threads when large), not the runtime's pageable-copy path; a call that fits one
@@ -1798,7 +1859,8 @@ int run_host_pipeline(vqhip_codec* c, bool is_encode, const void* in, void* out,
             if (out_ptrs) scatter_leaves(out_ptrs + ch.o, static_cast<const float*>(ch.result), ch.m);
             else host_parallel_copy(static_cast<char*>(out) + (size_t)ch.o * out_b, ch.result, (size_t)ch.m * out_b);
             return VQHIP_OK;
-        });
+        },
+        nullptr, decode_precision);
 }
 
 }  // namespace
@@ -2008,7 +2070,7 @@ int vqhip_decode_device(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* 
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int64_t o = 0; o < n; o += c->chunk) {
         const int64_t m = std::min(c->chunk, n - o);
-        int rc = decode_chunk(c, d_idx + o * 64, m, d_out + o * 512, s);
+        int rc = decode_chunk(c, d_idx + o * 64, m, d_out + o * 512, s, c->decode_precision);
         if (rc) return rc;
     }
     return VQHIP_OK;
@@ -2025,7 +2087,7 @@ int vqhip_decode(vqhip_codec* c, const uint8_t* indices, int64_t n, float* leave
 {
     if (!c) return VQHIP_ERR_INVALID;
     if (!leaves || !indices || n < 1) return fail(c, VQHIP_ERR_INVALID, "decode: null pointer or n_leaves < 1");
-    return run_host_pipeline(c, false, indices, leaves, n);
+    return run_host_pipeline(c, false, indices, leaves, n, nullptr, nullptr, c->decode_precision);
 }
 
 int vqhip_encode_leaves(vqhip_codec* c, const float* const* leaf_ptrs, int64_t n, uint8_t* indices)
@@ -2039,7 +2101,7 @@ int vqhip_decode_leaves(vqhip_codec* c, const uint8_t* indices, int64_t n, float
 {
     if (!c) return VQHIP_ERR_INVALID;
     if (!leaf_ptrs || !indices || n < 1) return fail(c, VQHIP_ERR_INVALID, "decode_leaves: null pointer or n_leaves < 1");
-    return run_host_pipeline(c, false, indices, nullptr, n, nullptr, leaf_ptrs);
+    return run_host_pipeline(c, false, indices, nullptr, n, nullptr, leaf_ptrs, c->decode_precision);
 }
 
 // ---- codebook training (stage 1): VectorQuantizerEMA.forward in training mode, VQVAE_v2.py:107-156 ----
@@ -2387,6 +2449,27 @@ static int multi_run(vqhip_multi* m, bool is_encode, const void* in, void* out, 
 
 int vqhip_multi_encode(vqhip_multi* m, const float* leaves, int64_t n, uint8_t* indices) { return multi_run(m, true, leaves, indices, n); }
 int vqhip_multi_decode(vqhip_multi* m, const uint8_t* indices, int64_t n, float* leaves) { return multi_run(m, false, indices, leaves, n); }
+
+// include/vqvdb_hip_precision.h
+int vqhip_set_decode_mode(vqhip_codec* c, int mode)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (mode != VQHIP_PRECISION_FP32 && mode != VQHIP_PRECISION_BF16)
+        return fail(c, VQHIP_ERR_INVALID, "set_decode_mode: mode " + std::to_string(mode) + " is neither VQHIP_PRECISION_FP32 (0) nor VQHIP_PRECISION_BF16 (1)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mode == VQHIP_PRECISION_BF16)
+        if (int rc = ensure_bf16_frags(c, c->stream)) return rc;   // (a failed allocation: VQHIP_ERR_NOMEM, the mode as it was)
+    c->decode_precision = mode;
+    return VQHIP_OK;
+}
+
+int vqhip_get_decode_mode(const vqhip_codec* c, int* mode)
+{
+    if (!c || !mode) return VQHIP_ERR_INVALID;
+    *mode = c->decode_precision;
+    return VQHIP_OK;
+}
 
 int vqhip_debug_enable(vqhip_codec* c, int enable)
 {

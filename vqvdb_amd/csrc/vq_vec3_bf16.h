@@ -17,21 +17,13 @@
 // consecutive taps (PAIR): 14 MFMAs for 27 taps, 81 of 224 K slots real.
 #pragma once
 
+#include "vq_bf16.h"   // v3b::bf16_bits
 #include "vq_vec3.h"
 
 namespace v3b {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// fp32 -> bf16 bits, round to nearest even (NaN stays a quiet NaN); what torch's .to(torch.bfloat16) does
-__host__ __device__ inline uint32_t bf16_bits(float v)
-{
-    uint32_t u;
-    __builtin_memcpy(&u, &v, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x40u;
-    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
 
 // LDS image of one leaf: NPI rows of CINP bf16.  off(pos, chunk) is the byte offset of 8 channels of a position.
 // Stride-1 convs read 32 consecutive positions (shifted by the tap) per wave: the key is the row's index among the rows
