@@ -18,7 +18,8 @@ __global__ void fill_k(float* p, size_t n, unsigned seed, float lo, float hi)
 }
 static void fill(float* p, size_t n, unsigned seed, float lo = -1.0f, float hi = 1.0f) { hipLaunchKernelGGL(fill_k, dim3(2048), dim3(256), 0, 0, p, n, seed, lo, hi); }
 
-constexpr size_t LDS_TAIL = (size_t)2 * (8 * 4 * 64) * 16;   // 2 x 32 KB weight window (vq_runtime.hip LDS_DEC_TAIL)
+constexpr size_t LDS_TAIL = mfma32_lds<DecTailSlab>();   // 2 x 32 KB weight window
+template <int A, int WM = 0> struct T_ : DecTailSlab { static constexpr int ABL = A, WMODE = WM; };   // the library's configuration with an ablation mask
 template <typename K>
 static float run(const char* name, K k, ConvArgs A, const int4* steps)
 {
@@ -61,10 +62,10 @@ int main()
     ConvArgs A{};
     A.in = in, A.out = out, A.wfrag = w, A.bias_frag = bias, A.se_csum = csum, A.se_fc0 = fc0, A.se_fc2 = fc2, A.n_tiles = nt, A.n_leaves = (int64_t)nt * 32;
     A.n_steps = (int)st.size() / 4;
-#define T(ABL) run("folded tail, ABL " #ABL, conv_mfma32_k<64, 128, 64, 4, 8, true, 1, 2, 0, false, 0, false, 2, ABL>, A, steps)
+#define T(ABL) run("folded tail, ABL " #ABL, conv_mfma32_k<T_<ABL>>, A, steps)
     // ABL bits: 1 no barriers, 2 no weight streaming, 4 no LDS A-fragment reads, 8 no activation re-loads, 16 no gate multiply, 32 no epilogue,
     // 64 no row-blocked totals, 128 no MFMAs
-#define TW(ABL, WM) run("folded tail, ABL " #ABL " WMODE " #WM, conv_mfma32_k<64, 128, 64, 4, 8, true, 1, 2, 0, false, 0, false, 2, ABL, WM>, A, steps)
+#define TW(ABL, WM) run("folded tail, ABL " #ABL " WMODE " #WM, (conv_mfma32_k<T_<ABL, WM>>), A, steps)
     T(0); TW(0, 0); TW(0, 1); TW(0, 0); TW(0, 1);   // (T = the library's WMODE 0)
     T(1); T(2); T(3); T(4); T(8); T(16); T(32); T(64); T(127); T(128); TW(8, 0); TW(2, 0); T(0);
     return 0;

@@ -35,7 +35,15 @@ static std::vector<int> steps_rows(int SI, int SO, int KS, int STRIDE, int PAD)
     return t;
 }
 
-constexpr size_t LDS = (size_t)2 * (3 * 16 * 64) * 16;
+constexpr size_t LDS = rows_lds<DecR64C1Full>();
+// the library's configurations (vq_kernels.h) with an ablation mask; the older orders (kw-inner, two-step prefetch) and OWI live only here
+template <int A> struct R_ : DecR64C1 { static constexpr int ABL = A; };                                        // kw-inner
+template <int A, int O = 1> struct RK_ : DecR64C1Full { static constexpr int ABL = A, OWI = O; };               // kw-outer, O outputs per MFMA run
+template <int A> struct R32_ : EncR32C1Full { static constexpr int ABL = A; static constexpr bool KWO = false; };
+template <int A> struct R32K_ : EncR32C1Full { static constexpr int ABL = A; };
+template <int A> struct R32K8_ : EncR32C1 { static constexpr int ABL = A; };                                    // 8 waves
+template <int A> struct RD_ : EncDownFull { static constexpr int ABL = A; static constexpr bool PF2 = true, KWO = false; };
+template <int A> struct RDK_ : EncDownFull { static constexpr int ABL = A; };
 template <typename K>
 static void run(const char* name, K k, ConvArgs A, const int4* steps, int nt)
 {
@@ -72,20 +80,20 @@ int main()
     ConvArgs A{};
     A.in = in, A.out = out, A.wfrag = w, A.bias_frag = bias, A.in_mean = mean, A.in_rstd = rstd, A.in_gamma = gam, A.in_beta = bet;
     A.out_mean = om, A.out_rstd = orr, A.n_tiles = nt, A.n_steps = (int)t.size() / 4, A.n_taps = 27;
-#define R(ABL) run("dec res64 conv1, ABL " #ABL, conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, false, ABL>, A, steps, nt)
+#define R(ABL) run("dec res64 conv1, ABL " #ABL, conv_rows16_k<R_<ABL>>, A, steps, nt)
     // ABL bits: 1 no barriers, 2 no weight streaming, 4 no LDS A reads, 8 no activation re-loads, 16 no GN transform, 32 no epilogue
     R(0); R(1); R(2); R(8); R(32); R(63);
-#define RK2(ABL) run("dec res64 conv1, kw-outer, 2 outputs per run, ABL " #ABL, conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, false, ABL, true, 2>, A, steps, nt)
-#define RK4(ABL) run("dec res64 conv1, kw-outer, 4 outputs per run, ABL " #ABL, conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, false, ABL, true, 4>, A, steps, nt)
-#define RK(ABL) run("dec res64 conv1, kw-outer, ABL " #ABL, conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, false, ABL, true>, A, steps, nt)
+#define RK2(ABL) run("dec res64 conv1, kw-outer, 2 outputs per run, ABL " #ABL, (conv_rows16_k<RK_<ABL, 2>>), A, steps, nt)
+#define RK4(ABL) run("dec res64 conv1, kw-outer, 4 outputs per run, ABL " #ABL, (conv_rows16_k<RK_<ABL, 4>>), A, steps, nt)
+#define RK(ABL) run("dec res64 conv1, kw-outer, ABL " #ABL, conv_rows16_k<RK_<ABL>>, A, steps, nt)
     RK(0); RK(128); RK(8); RK(16); RK(32); RK(64); RK(63);
     RK(0); RK2(0); RK4(0); RK(0); RK2(0); RK4(0); RK2(63); RK4(63);
     {   // encoder res32 conv1: 32 -> 32 k3 @4^3, weights LDS-resident (108 KB), 16 waves
         std::vector<int> t2 = steps_rows(4, 4, 3, 1, 1);
         ConvArgs B = A;
         B.n_taps = 27;
-        constexpr size_t LDS32 = (size_t)27 * (2 * 2 * 64) * 16;
-#define R32(ABL) { auto k = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true, 1, false, 16, false, ABL>; \
+        constexpr size_t LDS32 = rows_lds<EncR32C1Full>();
+#define R32(ABL) { auto k = conv_rows16_k<R32_<ABL>>; \
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS32); \
         hipEvent_t a, b; hipEventCreate(&a), hipEventCreate(&b); \
         for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(k, dim3((2 * nt + 15) / 16), dim3(1024), LDS32, 0, B, steps); \
@@ -93,7 +101,7 @@ int main()
         hipEventRecord(b, 0); hipEventSynchronize(b); float ms; hipEventElapsedTime(&ms, a, b); \
         printf("enc res32 conv1, ABL %-3d                                  %8.4f ms  (%s)\n", ABL, ms / 5, hipGetErrorString(hipGetLastError())); }
         R32(0) R32(8) R32(32) R32(60)
-#define R32K(ABL) { auto k = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true, 1, false, 16, false, ABL, true>; \
+#define R32K(ABL) { auto k = conv_rows16_k<R32K_<ABL>>; \
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS32); \
         hipEvent_t a, b; hipEventCreate(&a), hipEventCreate(&b); \
         for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(k, dim3((2 * nt + 15) / 16), dim3(1024), LDS32, 0, B, steps); \
@@ -101,7 +109,7 @@ int main()
         hipEventRecord(b, 0); hipEventSynchronize(b); float ms; hipEventElapsedTime(&ms, a, b); \
         printf("enc res32 conv1, kw-outer, ABL %-3d                        %8.4f ms  (%s)\n", ABL, ms / 5, hipGetErrorString(hipGetLastError())); }
         R32K(0) R32K(128)
-#define R32K8(ABL) { auto k = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true, 1, false, 8, false, ABL, true>; \
+#define R32K8(ABL) { auto k = conv_rows16_k<R32K8_<ABL>>; \
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS32); \
         hipEvent_t a, b; hipEventCreate(&a), hipEventCreate(&b); \
         for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(k, dim3((2 * nt + 7) / 8), dim3(512), LDS32, 0, B, steps); \
@@ -117,8 +125,8 @@ int main()
         hipMemcpy(steps3, t3.data(), t3.size() * 4, hipMemcpyHostToDevice);
         ConvArgs B = A;
         B.n_taps = 64, B.n_steps = (int)t3.size() / 4;
-        constexpr size_t LDSD = (size_t)64 * (1 * 2 * 64) * 16;
-#define RD(ABL) { auto k = conv_rows16_k<16, 32, 8, 4, 4, 2, 1, 0, false, 8, false, true, 1, true, 8, false, ABL>; \
+        constexpr size_t LDSD = rows_lds<EncDownFull>();
+#define RD(ABL) { auto k = conv_rows16_k<RD_<ABL>>; \
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSD); \
         hipEvent_t a, b; hipEventCreate(&a), hipEventCreate(&b); \
         for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(k, dim3((2 * nt + 7) / 8), dim3(512), LDSD, 0, B, steps3); \
@@ -126,7 +134,7 @@ int main()
         hipEventRecord(b, 0); hipEventSynchronize(b); float ms; hipEventElapsedTime(&ms, a, b); \
         printf("enc down, ABL %-3d                                         %8.4f ms  (%s)\n", ABL, ms / 5, hipGetErrorString(hipGetLastError())); }
         RD(0) RD(8) RD(32) RD(44)
-#define RDK(ABL) { auto k = conv_rows16_k<16, 32, 8, 4, 4, 2, 1, 0, false, 8, false, true, 1, false, 8, false, ABL, true>; \
+#define RDK(ABL) { auto k = conv_rows16_k<RDK_<ABL>>; \
         hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSD); \
         hipEvent_t a, b; hipEventCreate(&a), hipEventCreate(&b); \
         for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(k, dim3((2 * nt + 7) / 8), dim3(512), LDSD, 0, B, steps3); \

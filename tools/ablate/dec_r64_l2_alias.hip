@@ -37,7 +37,9 @@ static std::vector<int> steps_rows(int SI, int SO, int KS, int STRIDE, int PAD)
     return t;
 }
 
-constexpr size_t LDS = (size_t)2 * (3 * 16 * 64) * 16;
+constexpr size_t LDS = rows_lds<DecR64C1Full>();
+template <int A> struct C1_ : DecR64C1Full { static constexpr int ABL = A; };   // the library's configurations with an ablation mask
+template <int A> struct C2_ : DecR64C2Full { static constexpr int ABL = A; };
 template <typename K>
 static void run(const char* name, K k, ConvArgs A, const int4* steps, int nt)
 {
@@ -73,8 +75,8 @@ int main()
     ConvArgs A{};
     A.in = in, A.out = out, A.skip = skip, A.wfrag = w, A.bias_frag = bias, A.in_mean = mean, A.in_rstd = rstd, A.in_gamma = gam, A.in_beta = bet;
     A.out_mean = om, A.out_rstd = orr, A.out_csum = csum, A.n_tiles = nt, A.n_steps = (int)t.size() / 4, A.n_taps = 27;
-#define C1(ABL) run("dec_res64_conv1 (library instantiation), ABL " #ABL, conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, false, ABL, true>, A, steps, nt)
-#define C2(ABL) run("dec_res64_conv2 (library instantiation), ABL " #ABL, conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, true, false, 1, false, 8, false, ABL, true>, A, steps, nt)
+#define C1(ABL) run("dec_res64_conv1 (library instantiation), ABL " #ABL, conv_rows16_k<C1_<ABL>>, A, steps, nt)
+#define C2(ABL) run("dec_res64_conv2 (library instantiation), ABL " #ABL, conv_rows16_k<C2_<ABL>>, A, steps, nt)
     for (int r = 0; r < 3; ++r) { C1(0); C1(64); C2(0); C2(64); }
     C1(63);
     return 0;

@@ -22,21 +22,21 @@ def kernel_build_id():
             h.update(open(os.path.join(root, name), "rb").read())
     return h.hexdigest()[:12]
 
-LAUNCH = [  # (regex on the kernel's demangled name, launch name used by the library's profiler)
+LAUNCH = [  # (regex on the kernel's demangled name, launch name used by the library's profiler); the two generic convs by configuration (vq_kernels.h)
     (r"conv_first_k<0[,>]", "enc_conv_first_stats"), (r"conv_first_k<1[,>]", "enc_conv_first_gn"),
     (r"conv_first_roll_k<0[,>]", "enc_conv_first_stats"), (r"conv_first_roll_k<1[,>]", "enc_conv_first_gn"),   # round 4: rolling row window (normalising pass)
     (r"conv_first_once_k", "enc_conv_first"),   # the conv issued once: an 8-leaf group's output in the accumulators of one workgroup (vq_first_once.h)
     (r"conv8_c16_k<4, false, true, false>", "enc_res16_conv1"), (r"conv8_c16_k<4, true, false, false>", "enc_res16_conv2"),
     (r"conv8_lds_k<false, true", "enc_res16_conv1"), (r"conv8_lds_k<true, false", "enc_res16_conv2"),   # persistent grid = CUs: the large-batch launches
-    (r"conv_rows16_k<16, 32, 8, 4, 4, 2, 1, 0, false, 8, false, true[,>]", "enc_down"),
-    (r"conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true[,>]", "enc_res32_conv1"),
-    (r"conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, true, 0, true, true[,>]", "enc_res32_conv2"),
+    (r"conv_rows16_k<EncDown\w*>", "enc_down"),
+    (r"conv_rows16_k<EncR32C1\w*>", "enc_res32_conv1"),
+    (r"conv_rows16_k<EncR32C2\w*>", "enc_res32_conv2"),
     (r"conv_down_lds_k", "enc_down"), (r"conv4_lds_k<false, true, false", "enc_res32_conv1"), (r"conv4_lds_k<true, false, true", "enc_res32_conv2"),   # round 4: LDS plane rings
     (r"vq_folded_k<8[,>]", "enc_vq"), (r"pack_leaves_k", "pack_leaves"), (r"stem_lut_k", "dec_stem"),
     (r"gn_relu_stats_k<64", "dec_gn_relu_stats"), (r"stem_fused_k", "dec_stem_gn"), (r"stem_taps_k", "dec_stem_gn"),
-    (r"conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false[,>]", "dec_res64_conv1"),
-    (r"conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, true, false[,>]", "dec_res64_conv2"),
-    (r"tail_rows16_k<", "dec_tail"), (r"tail_rows32_k<", "dec_tail_rows32"), (r"tail_groups16_k<", "dec_tail_groups"), (r"conv_mfma32_k<64, 128, 64, 4, 8,", "dec_tail_slab"),
+    (r"conv_rows16_k<DecR64C1\w*>", "dec_res64_conv1"),
+    (r"conv_rows16_k<DecR64C2\w*>", "dec_res64_conv2"),
+    (r"tail_rows16_k<", "dec_tail"), (r"tail_rows32_k<", "dec_tail_rows32"), (r"tail_groups16_k<", "dec_tail_groups"), (r"conv_mfma32_k<DecTailSlab>", "dec_tail_slab"),
 ]
 
 

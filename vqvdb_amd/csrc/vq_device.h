@@ -28,7 +28,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 #define VQ_LT 32  // leaves per tile
 
-// Timing-only ablation switches (template parameter ABL of conv8_lds_k / conv_rows16_k, the STEM_DEPTH / WGRAD_ABL / ROWS4_PIPE macros) exist
+// Timing-only ablation switches (template parameter ABL of conv8_lds_k, field ABL of a conv_rows16_k / conv_mfma32_k configuration, the STEM_DEPTH / WGRAD_ABL / ROWS4_PIPE macros) exist
 // for tools/ablate/*.hip, which define VQ_ABLATE before including the kernel headers; a library build cannot instantiate them.
 #ifndef VQ_ABLATE
 #define VQ_ABLATE 0

@@ -566,12 +566,10 @@ __global__ __launch_bounds__(256, 2) void conv8_c16_k(ConvArgs A, const int4* __
 //     wait(prefetched B(s), W(s)) -> [barrier] -> issue B(s+1) loads (+ async global->LDS copy of
 //     W(s+1) into the other LDS buffer) -> NU*NMT*4 MFMAs on B(s) with the LDS A-fragment read
 //     one group ahead -> epilogue on the last tap of a position.
-// Weights are either fully LDS-resident (STREAM=false: encoder 4^3 layers, <=128 KB) or streamed
-// one tap per step through a double-buffered LDS window, all waves of the workgroup in lock-step
-// (STREAM=true: decoder layers, 0.4-1.8 MB of weights).
+// Weights are streamed one tap per step through a double-buffered LDS window, all waves of the
+// workgroup in lock-step (decoder layers, 0.4-1.8 MB of weights).
 //   INMODE 0: raw input      1: relu(GroupNorm(GIN)) on load      2: squeeze-excite gate on load
-//   RESID  : out = skip + 0.1*(acc+bias)        GOUT: GroupNorm statistics of the output
-//   CSUM   : per-channel sums of the output (feeds ChannelAttention of the next kernel)
+//   RESID  : out = skip + 0.1*(acc+bias)
 //   OUTMODE 0: store the leaf-tile activation.  2: folded decoder tail — the "positions" are the four
 //            128-voxel output slabs, the "taps" the input positions of the slab's receptive field, the
 //            rows of the weight fragments output VOXELS; epilogue = per-voxel bias, sigmoid, store into
@@ -590,16 +588,43 @@ __device__ __forceinline__ bool vq_tail_plane_needs(int od, int pd) { return pd 
 // counts that leave the younger re-loads in flight either way, and the two modes time the same (profiles/r04_ablate_folded_tail.txt).
 // ABL (tools/ablate/conv_mfma32_ablate.hip only): 1 no barriers, 2 no weight streaming, 4 no LDS A-fragment reads, 8 no activation
 // re-loads, 16 no input transform, 32 no epilogue, 64 no row-blocked totals, 128 no MFMAs
-template <int CIN, int COUT, int NPI, int NPO, int NW, bool STREAM, int KWG, int INMODE, int GIN, bool RESID, int GOUT,
-          bool CSUM, int OUTMODE, int ABL = 0, int WMODE = 0>
-__global__ __launch_bounds__(NW * 64, 2) void conv_mfma32_k(ConvArgs A, const int4* __restrict__ steps)
+// Every instantiation streams its weights (the LDS-resident variant went with the encoder's 4^3 layers), and the fused statistics of
+// this kernel predate the 16-block contract (no instantiation uses them): STREAM, GOUT and CSUM are no longer parameters.
+//
+// A configuration is a named struct derived from Mfma32Cfg (the defaults) that states what differs; block size and dynamic LDS of a
+// launch follow from it (mfma32_lds).  The library's configurations:
+struct Mfma32Cfg {
+    static constexpr int KWG = 1, INMODE = 0, GIN = 0, OUTMODE = 0, ABL = 0, WMODE = 0;
+    static constexpr bool RESID = false;
+};
+struct DecTailSlab : Mfma32Cfg { static constexpr int CIN = 64, COUT = 128, NPI = 64, NPO = 4, NW = 8, INMODE = 2, OUTMODE = 2; };   // folded up_conv+pixshuf+final (VQHIP_TAIL=slab)
+// Training forward / data-gradient convolutions (no fused statistics).  The 128-wide layers keep a 64 KB weight window in LDS, i.e. two
+// workgroups per CU: four tiles (waves) per workgroup give two waves per SIMD.
+struct TrainStem : Mfma32Cfg { static constexpr int CIN = 128, COUT = 64, NPI = 64, NPO = 64, NW = 4; };                // stem forward; also the up_conv^T halves
+struct TrainUp : Mfma32Cfg { static constexpr int CIN = 64, COUT = 128, NPI = 64, NPO = 64, NW = 4, INMODE = 2; };      // up_conv halves, SE gate on load
+struct DgradStem : Mfma32Cfg { static constexpr int CIN = 64, COUT = 128, NPI = 64, NPO = 64, NW = 4; };                // stem^T
+struct DgradTail : Mfma32Cfg { static constexpr int CIN = 128, COUT = 64, NPI = 4, NPO = 64, NW = 4; };   // folded tail^T (vq_train_tail.h): the 4 output slabs as input positions (128 voxels = channels), 64 output positions
+struct DgradProj : Mfma32Cfg { static constexpr int CIN = 128, COUT = 32, NPI = 64, NPO = 64, NW = 2; };                // proj^T (one tap)
+
+// dynamic LDS of a launch: the double-buffered window of KWG taps (the kernel's WSTEP float4, twice)
+template <class Cfg>
+constexpr size_t mfma32_lds()
 {
+    return (size_t)2 * Cfg::KWG * (Cfg::CIN / 8) * (Cfg::COUT / 32) * 64 * 16;
+}
+static_assert(mfma32_lds<DecTailSlab>() == 65536 && mfma32_lds<TrainStem>() == 65536 && mfma32_lds<TrainUp>() == 65536, "2 x 32 KB weight window");
+static_assert(mfma32_lds<DgradStem>() == 65536 && mfma32_lds<DgradTail>() == 65536 && mfma32_lds<DgradProj>() == 32768, "2 x 32 KB / 2 x 16 KB weight window");
+
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::NW * 64, 2) void conv_mfma32_k(ConvArgs A, const int4* __restrict__ steps)
+{
+    constexpr int CIN = Cfg::CIN, COUT = Cfg::COUT, NPI = Cfg::NPI, NPO = Cfg::NPO, NW = Cfg::NW, KWG = Cfg::KWG, INMODE = Cfg::INMODE, GIN = Cfg::GIN;
+    constexpr int OUTMODE = Cfg::OUTMODE, ABL = Cfg::ABL, WMODE = Cfg::WMODE;
+    constexpr bool RESID = Cfg::RESID;
     static_assert(ABL == 0 || VQ_ABLATE, "ABL is a timing-only ablation switch (tools/ablate, -DVQ_ABLATE=1)");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     f32x4* lds = (f32x4*)smem_raw;
     constexpr int NU = CIN / 8, NMT = COUT / 32, NK = NU * NMT;
-    static_assert(STREAM, "every instantiation streams its weights (the LDS-resident variant went with the encoder's 4^3 layers)");
-    static_assert(GOUT == 0 && !CSUM, "the fused statistics of this kernel predate the 16-block contract (no instantiation uses them)");
     // One step = KWG consecutive taps (input positions e.x .. e.x + KWG - 1, fragments e.y .. e.y + KWG - 1) = NGR groups of one
     // channel octet x NMT cout tiles.  The next step's WSTEP float4 of weights travel global -> register -> LDS in 1 KiB pieces, one
     // piece per wave every few groups (requested at the group's start, stored after its MFMAs: see REGW in conv_rows16_k for why not
@@ -994,9 +1019,87 @@ __global__ __launch_bounds__(256) void tail_small16_k(ConvArgs A)
 // -> 91-93 % at 2.38 GHz (buffer addressing, REGW, lazy arrival).
 // wfrag[((tap*CBN + cb)*MTN + mt)*64 + lane][i] = W[16mt + (lane&15)][16cb + 4(lane>>4) + i][tap];  bias: plain [COUT].
 // ------------------------------------------------------------------------------------------
-template <int CIN, int COUT, int SI, int SO, int KS, int STRIDE, int PAD, int INMODE, bool RESID, int GOUT, bool CSUM, bool RESIDENT = false, int MSPLIT = 1, bool PF2 = false, int NWV = 8, bool PARTS = false, int ABL = 0, bool KWO = false, int OWI = 1>
-__global__ __launch_bounds__(NWV * 64, 1) void conv_rows16_k(ConvArgs A, const int4* __restrict__ steps)
+//
+// A configuration is a named struct: RowsCfg holds the defaults, a per-layer base the shape, and each instantiation states what differs.
+// Workgroup size (NWV x 64), gridDim.z (MSPLIT) and the dynamic LDS of a launch (rows_lds) follow from it.
+//   INMODE 0: raw input  1: relu(GroupNorm(8)) on load     RESID: out = skip + 0.1*(acc+bias)     GOUT: GroupNorm statistics of the output
+//   CSUM: per-channel sums of the output (attention)       PARTS: the statistics as per-block partials (position-split launches)
+//   RESIDENT: the layer's weights stay in LDS              MSPLIT: cout blocks over gridDim.z      NWV: half tiles (waves) per workgroup
+//   KWO: kw-outer MFMA order    PF2 / OWI (tools/ablate only): two-step prefetch / outputs per MFMA run    ABL: see the kernel
+struct RowsCfg {
+    static constexpr bool RESID = false, CSUM = false, RESIDENT = false, PF2 = false, PARTS = false, KWO = false;
+    static constexpr int GOUT = 0, MSPLIT = 1, NWV = 8, ABL = 0, OWI = 1;
+};
+// decoder ResidualBlock(64): conv1 carries the statistics of gn2, conv2 the residual and the channel sums of the attention
+struct DecR64 : RowsCfg { static constexpr int CIN = 64, COUT = 64, SI = 4, SO = 4, KS = 3, STRIDE = 1, PAD = 1, INMODE = 1; };
+struct DecR64C1 : DecR64 { static constexpr int GOUT = 8; };
+struct DecR64C2 : DecR64 { static constexpr bool RESID = true, CSUM = true; };
+struct DecR64C1Full : DecR64C1 { static constexpr bool KWO = true; };   // full chunks: kw-outer (A fragments of a (kw, channel-block pair) read once for every output of the row)
+struct DecR64C2Full : DecR64C2 { static constexpr bool KWO = true; };
+struct DecR64C1Split : DecR64C1 { static constexpr bool PARTS = true; };   // position-split launches (kw-outer would spill here: the per-block statistics partials)
+struct DecR64C2Split : DecR64C2 { static constexpr bool PARTS = true, KWO = true; };   // kw-outer, register-staged weights: 309 -> 290 us at 4096 leaves
+// ... that additionally split the output channels over gridDim.z (a wave's serial MFMA chain is the latency of a small batch)
+struct DecR64C1Split4 : DecR64C1Split { static constexpr int MSPLIT = 4; };
+struct DecR64C2Split4 : DecR64C2 { static constexpr bool PARTS = true; static constexpr int MSPLIT = 4; };
+// ... with the quarter's weights of the whole layer LDS-resident (27 taps x 4 KB = 108 KB): no per-step barrier, no streaming
+struct DecR64C1Split4Res : DecR64C1Split4 { static constexpr bool RESIDENT = true, KWO = true; };
+struct DecR64C2Split4Res : DecR64C2Split4 { static constexpr bool RESIDENT = true, KWO = true; };
+// the same layer without fused statistics: training forward ...
+struct TrainR64C1 : DecR64 { static constexpr bool KWO = true; };
+struct TrainR64C2 : DecR64 { static constexpr bool RESID = true, KWO = true; };
+// ... as four cout quarters with LDS-resident weights for small training batches (up to 2048 leaves) — inference's choice for such passes.
+// With one workgroup per (8 half tiles, output row) the launch has exactly as many workgroups as the chip has CUs and a row costs 4, 6 or
+// 9 (kd, kh) steps (corner / edge / interior): the CUs with corner rows idle for half of the kernel (average 6.25 steps against 9: 0.69).
+// Four times as many workgroups of a quarter of the work each are handed out as CUs free up.
+struct TrainR64C1Split4Res : TrainR64C1 { static constexpr bool RESIDENT = true; static constexpr int MSPLIT = 4; };
+struct TrainR64C2Split4Res : TrainR64C2 { static constexpr bool RESIDENT = true; static constexpr int MSPLIT = 4; };
+// ... and its data gradient, res64 conv^T (raw input)
+struct DgradR64 : DecR64 { static constexpr int INMODE = 0; static constexpr bool KWO = true; };
+struct DgradR64Split4Res : DgradR64 { static constexpr bool RESIDENT = true; static constexpr int MSPLIT = 4; };
+// The data gradients run beside the weight-gradient kernels (52-76 KB of LDS on every CU): cout quarters / halves with STREAMED weight
+// windows (24 KB / 12 KB of LDS), so that a chain workgroup fits on a CU beside a weight-gradient workgroup.  With 98-110 KB the 32 -> 32
+// data gradient waited for the stem's weight gradient to leave the CUs: 356 us against 51 us alone
+// (profiles/r06_train_step_timeline_2048_deferred_reductions.txt).
+struct DgradR64Split4 : DgradR64 { static constexpr int MSPLIT = 4; static constexpr bool KWO = false; };
+// encoder down conv 16 -> 32 k4 s2: weights LDS-resident (128 KB), kw-outer with fragments read a group ahead
+struct EncDown : RowsCfg { static constexpr int CIN = 16, COUT = 32, SI = 8, SO = 4, KS = 4, STRIDE = 2, PAD = 1, INMODE = 0, GOUT = 8; static constexpr bool RESIDENT = true, KWO = true; };
+struct EncDownFull : EncDown {};                                                // full chunks, 8 waves
+struct EncDownSplit : EncDown { static constexpr bool PARTS = true; };          // position-split launches (8-wave workgroups), per-block partials
+struct EncDownSplit2 : EncDownSplit { static constexpr int MSPLIT = 2; };       // ... and the 32 couts over gridDim.z
+// encoder ResidualBlock(32): weights LDS-resident (108 KB), kw-outer
+struct EncR32 : RowsCfg { static constexpr int CIN = 32, COUT = 32, SI = 4, SO = 4, KS = 3, STRIDE = 1, PAD = 1, INMODE = 1; static constexpr bool RESIDENT = true, KWO = true; };
+struct EncR32C1 : EncR32 { static constexpr int GOUT = 8; };
+struct EncR32C2 : EncR32 { static constexpr bool RESID = true, CSUM = true; };
+struct EncR32C1Full : EncR32C1 { static constexpr int NWV = 16; };   // full chunks: 16 waves behind one LDS copy (4/SIMD)
+struct EncR32C2Full : EncR32C2 { static constexpr int NWV = 16; };
+struct EncR32C1Split : EncR32C1 { static constexpr bool PARTS = true; };
+struct EncR32C2Split : EncR32C2 { static constexpr bool PARTS = true; };
+struct EncR32C1Split2 : EncR32C1Split { static constexpr int MSPLIT = 2; };
+struct EncR32C2Split2 : EncR32C2Split { static constexpr int MSPLIT = 2; };
+struct DgradR32 : EncR32 { static constexpr int INMODE = 0; };                  // res32 conv^T (raw input, resident weights)
+struct DgradR32Split2 : DgradR32 { static constexpr bool RESIDENT = false, KWO = false; static constexpr int MSPLIT = 2; };   // streamed halves (12 KB), see DgradR64Split4
+
+// dynamic LDS of a launch: all KS^3 taps of this workgroup's cout blocks (RESIDENT), or the double-buffered window of one step's KS taps
+// (the kernel's WTAPL / WSTEPL float4)
+template <class Cfg>
+constexpr size_t rows_lds()
 {
+    constexpr size_t WTAP = (Cfg::CIN / 16) * (Cfg::COUT / 16) * 64, WSTEP = Cfg::KS * WTAP;
+    constexpr size_t WTAPL = WTAP / Cfg::MSPLIT, WSTEPL = WSTEP / Cfg::MSPLIT;
+    return Cfg::RESIDENT ? Cfg::KS * Cfg::KS * Cfg::KS * WTAPL * 16 : 2 * WSTEPL * 16;
+}
+static_assert(rows_lds<EncDownFull>() == 131072 && rows_lds<EncDownSplit2>() == 65536, "enc down: 64 taps resident, whole / cout halves");
+static_assert(rows_lds<EncR32C1Full>() == 110592 && rows_lds<DecR64C1Split4Res>() == 110592, "27 taps resident: res32 whole, res64 cout quarters");
+static_assert(rows_lds<EncR32C1Split2>() == 55296, "res32 resident, cout halves");
+static_assert(rows_lds<DecR64C1Full>() == 98304 && rows_lds<DecR64C1Split4>() == 24576 && rows_lds<DgradR64Split4>() == 24576, "res64 streamed: 2 x 48 KB, quarters");
+static_assert(rows_lds<DgradR32Split2>() == 12288, "res32 streamed, cout halves");
+
+template <class Cfg>
+__global__ __launch_bounds__(Cfg::NWV * 64, 1) void conv_rows16_k(ConvArgs A, const int4* __restrict__ steps)
+{
+    constexpr int CIN = Cfg::CIN, COUT = Cfg::COUT, SI = Cfg::SI, SO = Cfg::SO, KS = Cfg::KS, STRIDE = Cfg::STRIDE, PAD = Cfg::PAD, INMODE = Cfg::INMODE;
+    constexpr int GOUT = Cfg::GOUT, MSPLIT = Cfg::MSPLIT, NWV = Cfg::NWV, ABL = Cfg::ABL, OWI = Cfg::OWI;
+    constexpr bool RESID = Cfg::RESID, CSUM = Cfg::CSUM, RESIDENT = Cfg::RESIDENT, PF2 = Cfg::PF2, PARTS = Cfg::PARTS, KWO = Cfg::KWO;
     static_assert(ABL == 0 || VQ_ABLATE, "ABL is a timing-only ablation switch (tools/ablate, -DVQ_ABLATE=1)");
     // ABL: timing-only ablations for tools/ablate/conv_rows16_ablate.hip (0 in the library): 1 no barriers, 2 no weight streaming,
     // 4 no LDS A-fragment reads, 8 no activation re-loads, 16 no GroupNorm transform, 32 no epilogue, 64 every tile reads tile 0 (L2 hits)

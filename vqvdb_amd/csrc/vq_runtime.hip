@@ -8,6 +8,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <array>
 #include <cctype>
 #include <cerrno>
 #include <cstdlib>
@@ -23,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/vqvdb_hip.h"
@@ -1009,64 +1011,75 @@ int set_lds(vqhip_codec* c, K kernel, size_t bytes)
 }
 
 // kernel instantiations -------------------------------------------------------------------
-//                                          CIN COUT NPI NPO NW STREAM KWG INMODE GIN RESID GOUT CSUM  OUTMODE
-//                                        CIN COUT SI SO KS ST PD NW INMODE GIN RESID GOUT CSUM
 // decoder front of full chunks: gathers row by row (PIPE 0: the tap loop is bound by the LDS itself, reads in flight ahead bought nothing),
 // the two position halves of a leaf octet on one SIMD (HMAP 1), the first taps of a pass not waiting for the previous pass's stores (RELAX)
 constexpr auto k_stem_taps = stem_taps_k<0, 1, 0, true, 0, true>;   // (+ checkerboard row ownership: equal valid rows per wave in every tap)
-constexpr auto k_dec_tail = conv_mfma32_k<64, 128, 64, 4, 8, true, 1, 2, 0, false, 0, false, 2>;  // folded up_conv+pixshuf+final
-//                                           CIN COUT SI SO KS ST PD INMODE RESID GOUT CSUM
-// large passes: kw-outer MFMA order (A fragments of a (kw, channel-block pair) read once for every output of the row)
-constexpr auto k_dec_r64c1_r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, false, 0, true>;   // row-blocked 16x16x4 convs (4^3 outputs)
-constexpr auto k_dec_r64c2_r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, true, false, 1, false, 8, false, 0, true>;
-constexpr auto k_dec_r64c1_rs = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 0, false, false, 1, false, 8, false, 0, true>;  // ... without fused statistics (training forward, data gradients)
-constexpr auto k_dec_r64c2_rs = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, false, false, 1, false, 8, false, 0, true>;
-// position-split inference launches: fused statistics as per-block partials (PARTS)
-constexpr auto k_dec_r64c1_rp = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 1, false, 8, true>;   // (kw-outer would spill here: the per-block statistics partials)
-constexpr auto k_dec_r64c2_rp = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, true, false, 1, false, 8, true, 0, true>;   // kw-outer, register-staged weights: 309 -> 290 us at 4096 leaves
-constexpr auto k_enc_down_r = conv_rows16_k<16, 32, 8, 4, 4, 2, 1, 0, false, 8, false, true, 1, false, 8, false, 0, true>;      // 8 waves, kw-outer with fragments read a group ahead    // weights LDS-resident
-constexpr auto k_enc_down_rs = conv_rows16_k<16, 32, 8, 4, 4, 2, 1, 0, false, 8, false, true, 1, false, 8, true, 0, true>;   // position-split launches (8-wave workgroups), per-block partials
-constexpr auto k_enc_r32c1_r = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true, 1, false, 16, false, 0, true>;   // 16 waves behind one LDS copy (4/SIMD), kw-outer
-constexpr auto k_enc_r32c1_rs = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true, 1, false, 8, true, 0, true>;
-constexpr auto k_enc_r32c2_r = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, true, 0, true, true, 1, false, 16, false, 0, true>;
-constexpr auto k_enc_r32c2_rs = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, true, 0, true, true, 1, false, 8, true, 0, true>;
-constexpr size_t LDS_ENC_DOWN_R = (size_t)64 * (1 * 2 * 64) * 16;   // 128 KB, resident
-constexpr size_t LDS_ENC_R32R = (size_t)27 * (2 * 2 * 64) * 16;     // 108 KB, resident
-constexpr size_t LDS_DEC_R64R = (size_t)2 * (3 * 16 * 64) * 16;      // 2 x 48 KB weight window
-constexpr size_t LDS_DEC_TAIL = (size_t)2 * (8 * 4 * 64) * 16;    // 2 x 32 KB
 
-// position-split variants that additionally split the output channels over gridDim.z (a wave's serial MFMA chain is the latency
-// of a small batch): the 4^3 convs for the tiniest batches; the folded tail has its own small-batch kernel (tail_small_k)
-constexpr auto k_dec_r64c1_rs4 = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, false, 4, false, 8, true>;
-constexpr auto k_dec_r64c2_rs4 = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, true, false, 4, false, 8, true>;
-// ... with the quarter's weights of the whole layer LDS-resident (27 taps x 4 KB = 108 KB): no per-step barrier, no streaming
-constexpr auto k_dec_r64c1_rs4r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 8, false, true, 4, false, 8, true, 0, true>;
-constexpr auto k_dec_r64c2_rs4r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, true, true, 4, false, 8, true, 0, true>;
-constexpr size_t LDS_DEC_R64S4R = (size_t)27 * (4 * 1 * 64) * 16;
-constexpr auto k_enc_down_rs2 = conv_rows16_k<16, 32, 8, 4, 4, 2, 1, 0, false, 8, false, true, 2, false, 8, true, 0, true>;    // (statistics as per-block partials)
-constexpr auto k_enc_r32c1_rs2 = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, false, 8, false, true, 2, false, 8, true, 0, true>;
-constexpr auto k_enc_r32c2_rs2 = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 1, true, 0, true, true, 2, false, 8, true, 0, true>;
-// position-split (small-batch) variants: 2 tiles per workgroup, no fused statistics
+// The two generic convs, conv_rows16_k and conv_mfma32_k, are instantiated on the named configurations of vq_kernels.h.  Every
+// configuration the library launches stands in one of three lists: inference, and the decoder / encoder halves of the full training
+// step (vq_train_full.inc).  From a list follows the table of its kernels with their dynamic LDS, which the init functions walk
+// (set_lds); the launch helpers below refuse a configuration that is in no list.  Each table is defined where its kernels have
+// always been instantiated, in that order: the order of the kernels in the code object follows it.
+template <class... Cfg>
+struct ConvList {
+    template <class T>
+    static constexpr bool has = (std::is_same_v<T, Cfg> || ...);
+};
+using InferConvs = ConvList<DecTailSlab, DecR64C1Full, DecR64C2Full, TrainR64C1, TrainR64C2, DecR64C1Split, DecR64C2Split, EncDownFull, EncDownSplit,
+                            EncR32C1Full, EncR32C1Split, EncR32C2Full, EncR32C2Split, DecR64C1Split4, DecR64C2Split4, DecR64C1Split4Res, DecR64C2Split4Res,
+                            EncDownSplit2, EncR32C1Split2, EncR32C2Split2>;
+using TrainDecConvs = ConvList<TrainStem, TrainUp, DgradR64, DgradStem, TrainR64C1Split4Res, TrainR64C2Split4Res, DgradR64Split4Res, DgradR64Split4,
+                               DgradR32Split2, DgradTail>;
+using TrainEncConvs = ConvList<DgradProj, DgradR32>;
+
+struct ConvKernel {
+    void (*fn)(ConvArgs, const int4*);
+    size_t lds;
+};
+template <class Cfg>
+constexpr ConvKernel conv_kernel()
+{
+    if constexpr (std::is_base_of_v<RowsCfg, Cfg>) return {conv_rows16_k<Cfg>, rows_lds<Cfg>()};
+    else return {conv_mfma32_k<Cfg>, mfma32_lds<Cfg>()};
+}
+template <class... Cfg>
+constexpr std::array<ConvKernel, sizeof...(Cfg)> conv_kernels(ConvList<Cfg...>)
+{
+    return {{conv_kernel<Cfg>()...}};
+}
+template <size_t N>
+int set_lds(vqhip_codec* c, const std::array<ConvKernel, N>& kernels)
+{
+    for (const ConvKernel& k : kernels)
+        if (int rc = set_lds(c, k.fn, k.lds)) return rc;
+    return VQHIP_OK;
+}
+constexpr auto kInferConvs = conv_kernels(InferConvs{});
+
+// Launches of the two generic convs: block, grid and dynamic LDS follow from the configuration.  nt: leaf tiles of the batch; psplit:
+// gridDim.y, the ranges of output groups of a position-split launch.
+template <class Cfg>
+constexpr bool conv_listed = InferConvs::has<Cfg> || TrainDecConvs::has<Cfg> || TrainEncConvs::has<Cfg>;
+template <class Cfg>
+void launch_rows(hipStream_t s, const ConvArgs& A, const void* steps, int nt, int psplit = 1)
+{
+    static_assert(conv_listed<Cfg>, "list the configuration above: init sets the dynamic LDS limit of the listed kernels");
+    // NWV half tiles per workgroup, MSPLIT blocks of output channels over gridDim.z
+    hipLaunchKernelGGL(conv_rows16_k<Cfg>, dim3((2 * nt + Cfg::NWV - 1) / Cfg::NWV, psplit, Cfg::MSPLIT), dim3(Cfg::NWV * 64), rows_lds<Cfg>(), s, A, (const int4*)steps);
+}
+template <class Cfg>
+void launch_mfma32(hipStream_t s, const ConvArgs& A, const void* steps, int nt, int psplit = 1)
+{
+    static_assert(conv_listed<Cfg>, "list the configuration above: init sets the dynamic LDS limit of the listed kernels");
+    hipLaunchKernelGGL(conv_mfma32_k<Cfg>, dim3((nt + Cfg::NW - 1) / Cfg::NW, psplit), dim3(Cfg::NW * 64), mfma32_lds<Cfg>(), s, A, (const int4*)steps);   // NW tiles per workgroup
+}
 
 constexpr size_t LDS_LATENT = (16 * 8 * 64 + 4 * 4 * 64) * 16;  // codebook + projection A-fragments (144 KB)
 
 int init_kernel_attrs(vqhip_codec* c)
 {
     int rc;
-    if ((rc = set_lds(c, k_enc_down_r, LDS_ENC_DOWN_R))) return rc;
-    if ((rc = set_lds(c, k_enc_down_rs, LDS_ENC_DOWN_R))) return rc;
-    if ((rc = set_lds(c, k_enc_r32c1_r, LDS_ENC_R32R))) return rc;
-    if ((rc = set_lds(c, k_enc_r32c1_rs, LDS_ENC_R32R))) return rc;
-    if ((rc = set_lds(c, k_enc_r32c2_r, LDS_ENC_R32R))) return rc;
-    if ((rc = set_lds(c, k_enc_r32c2_rs, LDS_ENC_R32R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c1_r, LDS_DEC_R64R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c2_r, LDS_DEC_R64R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c1_rs, LDS_DEC_R64R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c2_rs, LDS_DEC_R64R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c1_rs4r, LDS_DEC_R64S4R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c2_rs4r, LDS_DEC_R64S4R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c1_rp, LDS_DEC_R64R))) return rc;
-    if ((rc = set_lds(c, k_dec_r64c2_rp, LDS_DEC_R64R))) return rc;
+    if ((rc = set_lds(c, kInferConvs))) return rc;
     if ((rc = set_lds(c, conv8_lds_k<false, true, 8, 0, true>, LDS_CONV8))) return rc;
     if ((rc = set_lds(c, conv8_lds_k<false, true, 16, 0, false>, LDS_CONV8))) return rc;
     if ((rc = set_lds(c, conv8_lds_k<true, false, 16, 0, false>, LDS_CONV8))) return rc;
@@ -1228,8 +1241,8 @@ int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, h
         A.n_steps = c->nsteps["steps.rows_k4s2_8"], A.n_taps = 64, A.grp_start = od("steps.rows_k4s2_8"), A.part_s = ps, A.part_q = pq;
         const int psr = split_factor(gh, 4, 16, 512);
         L.run("enc_down_s", [&] {
-            if (gh * psr * 2 <= 256) hipLaunchKernelGGL(k_enc_down_rs2, dim3(gh, psr, 2), dim3(512), LDS_ENC_DOWN_R / 2, s, A, (const int4*)w["steps.rows_k4s2_8"]);
-            else hipLaunchKernelGGL(k_enc_down_rs, dim3(gh, psr), dim3(512), LDS_ENC_DOWN_R, s, A, (const int4*)w["steps.rows_k4s2_8"]);
+            if (gh * psr * 2 <= 256) launch_rows<EncDownSplit2>(s, A, w["steps.rows_k4s2_8"], nt, psr);
+            else launch_rows<EncDownSplit>(s, A, w["steps.rows_k4s2_8"], nt, psr);
         });
         combine("enc_stats_x7", 8, 1.0 / 256.0, S.x7m, S.x7r);
     }
@@ -1241,16 +1254,16 @@ int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, h
         const int psr = split_factor(gh, 4, 16, 512);
         const bool ms = gh * psr * 2 <= 256;   // up to 1024 leaves (measured): also split the 32 couts over gridDim.z
         L.run("enc_res32_conv1_s", [&] {
-            if (ms) hipLaunchKernelGGL(k_enc_r32c1_rs2, dim3(gh, psr, 2), dim3(512), LDS_ENC_R32R / 2, s, A, (const int4*)w["steps.rows_k3_4"]);
-            else hipLaunchKernelGGL(k_enc_r32c1_rs, dim3(gh, psr), dim3(512), LDS_ENC_R32R, s, A, (const int4*)w["steps.rows_k3_4"]);
+            if (ms) launch_rows<EncR32C1Split2>(s, A, w["steps.rows_k3_4"], nt, psr);
+            else launch_rows<EncR32C1Split>(s, A, w["steps.rows_k3_4"], nt, psr);
         });
         combine("enc_stats_y9", 8, 1.0 / 256.0, S.y9m, S.y9r);
         A.in = a["e_y9"], A.out = a["e_x11"], A.wfrag = w["r32c2.w16"], A.bias_frag = w["r32c2.braw"], A.skip = a["e_x7"];
         A.in_mean = S.y9m, A.in_rstd = S.y9r, A.in_gamma = w["r32g2.w"], A.in_beta = w["r32g2.b"];
         A.part_s = nullptr, A.part_q = nullptr, A.part_c = a["part_c"];
         L.run("enc_res32_conv2_s", [&] {
-            if (ms) hipLaunchKernelGGL(k_enc_r32c2_rs2, dim3(gh, psr, 2), dim3(512), LDS_ENC_R32R / 2, s, A, (const int4*)w["steps.rows_k3_4"]);
-            else hipLaunchKernelGGL(k_enc_r32c2_rs, dim3(gh, psr), dim3(512), LDS_ENC_R32R, s, A, (const int4*)w["steps.rows_k3_4"]);
+            if (ms) launch_rows<EncR32C2Split2>(s, A, w["steps.rows_k3_4"], nt, psr);
+            else launch_rows<EncR32C2Split>(s, A, w["steps.rows_k3_4"], nt, psr);
         });
         L.run("enc_csum_x11", [&] { hipLaunchKernelGGL((csum_combine_k<32>), dim3(nt), dim3(256), 0, s, a["part_c"], S.csum, w["efc0"], w["efc2"], a["gate"]); });
     }
@@ -1350,7 +1363,7 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
         A.out_mean = S.x7m, A.out_rstd = S.x7r, A.n_tiles = nt;
         A.n_steps = c->nsteps["steps.rows_k4s2_8"], A.n_taps = 64;
         if (c->convdown_lds) L.run("enc_down", [&] { hipLaunchKernelGGL(conv_down_lds_k<0>, dim3(std::min(2 * nt, c->n_cus)), dim3(1024), LDS_CONVDOWN, s, A); });
-        else L.run("enc_down", [&] { hipLaunchKernelGGL(k_enc_down_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_ENC_DOWN_R, s, A, (const int4*)w["steps.rows_k4s2_8"]); });
+        else L.run("enc_down", [&] { launch_rows<EncDownFull>(s, A, w["steps.rows_k4s2_8"], nt); });
     }
     {
         ConvArgs A{};
@@ -1359,7 +1372,7 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
         A.out_mean = S.y9m, A.out_rstd = S.y9r, A.n_tiles = nt;
         A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
         if (c->conv4_lds) L.run("enc_res32_conv1", [&] { hipLaunchKernelGGL((conv4_lds_k<false, true, false, 0, 1>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV4, s, A); });
-        else L.run("enc_res32_conv1", [&] { hipLaunchKernelGGL(k_enc_r32c1_r, dim3((2 * nt + 15) / 16), dim3(1024), LDS_ENC_R32R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+        else L.run("enc_res32_conv1", [&] { launch_rows<EncR32C1Full>(s, A, w["steps.rows_k3_4"], nt); });
     }
     {
         ConvArgs A{};
@@ -1368,7 +1381,7 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
         A.out_csum = S.csum, A.n_tiles = nt;
         A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
         if (c->conv4_lds) L.run("enc_res32_conv2", [&] { hipLaunchKernelGGL((conv4_lds_k<true, false, true, 0, 0>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV4, s, A); });
-        else L.run("enc_res32_conv2", [&] { hipLaunchKernelGGL(k_enc_r32c2_r, dim3((2 * nt + 15) / 16), dim3(1024), LDS_ENC_R32R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+        else L.run("enc_res32_conv2", [&] { launch_rows<EncR32C2Full>(s, A, w["steps.rows_k3_4"], nt); });
     }
 
     if (d_latent) {
@@ -1491,18 +1504,18 @@ int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_
         const bool ms = gh * psr * 4 <= 1024;   // up to 2048 leaves (measured): also split the 64 couts over gridDim.z
         const bool r64res = c->r64s_resident;
         L.run("dec_res64_conv1_s", [&] {
-            if (ms && r64res) hipLaunchKernelGGL(k_dec_r64c1_rs4r, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64S4R, s, A, (const int4*)w["steps.rows_k3_4"]);
-            else if (ms) hipLaunchKernelGGL(k_dec_r64c1_rs4, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64R / 4, s, A, (const int4*)w["steps.rows_k3_4"]);
-            else hipLaunchKernelGGL(k_dec_r64c1_rp, dim3(gh, psr), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]);
+            if (ms && r64res) launch_rows<DecR64C1Split4Res>(s, A, w["steps.rows_k3_4"], nt, psr);
+            else if (ms) launch_rows<DecR64C1Split4>(s, A, w["steps.rows_k3_4"], nt, psr);
+            else launch_rows<DecR64C1Split>(s, A, w["steps.rows_k3_4"], nt, psr);
         });
         combine64("dec_stats_y4", a["st_a.mean"], a["st_a.rstd"]);
         A.in = a["d_y4"], A.out = a["d_x6"], A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.skip = a["d_d2"];
         A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
         A.part_s = nullptr, A.part_q = nullptr, A.part_c = a["part_c"];
         L.run("dec_res64_conv2_s", [&] {
-            if (ms && r64res) hipLaunchKernelGGL(k_dec_r64c2_rs4r, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64S4R, s, A, (const int4*)w["steps.rows_k3_4"]);
-            else if (ms) hipLaunchKernelGGL(k_dec_r64c2_rs4, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64R / 4, s, A, (const int4*)w["steps.rows_k3_4"]);
-            else hipLaunchKernelGGL(k_dec_r64c2_rp, dim3(gh, psr), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]);
+            if (ms && r64res) launch_rows<DecR64C2Split4Res>(s, A, w["steps.rows_k3_4"], nt, psr);
+            else if (ms) launch_rows<DecR64C2Split4>(s, A, w["steps.rows_k3_4"], nt, psr);
+            else launch_rows<DecR64C2Split>(s, A, w["steps.rows_k3_4"], nt, psr);
         });
         L.run("dec_csum_x6", [&] { hipLaunchKernelGGL((csum_combine_k<64>), dim3(nt), dim3(512), 0, s, a["part_c"], a["csum"], w["dfc0"], w["dfc2"], a["gate"]); });
     }
@@ -1534,7 +1547,7 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
     auto& a = c->act;
     auto& w = c->dw;
     Launcher L{c, s, n};
-    const int g4 = (nt + 3) / 4, g8 = (nt + 7) / 8;
+    const int g4 = (nt + 3) / 4;
 
     if (precision == VQHIP_PRECISION_BF16 && (rc = ensure_bf16_frags(c, s))) return rc;
     if (use_split(c, nt, true)) return decode_chunk_split(c, L, d_idx, n, d_out, s, precision);
@@ -1567,7 +1580,7 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
             A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"];
             A.out_mean = a["st_a.mean"], A.out_rstd = a["st_a.rstd"], A.n_tiles = nt;
             A.wfrag = w["r64c1.w16"], A.bias_frag = w["r64c1.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-            L.run("dec_res64_conv1", [&] { hipLaunchKernelGGL(k_dec_r64c1_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+            L.run("dec_res64_conv1", [&] { launch_rows<DecR64C1Full>(s, A, w["steps.rows_k3_4"], nt); });
         }
         {
             ConvArgs A{};
@@ -1575,7 +1588,7 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
             A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
             A.out_csum = a["csum"], A.n_tiles = nt;
             A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-            L.run("dec_res64_conv2", [&] { hipLaunchKernelGGL(k_dec_r64c2_r, dim3((2 * nt + 7) / 8), dim3(512), LDS_DEC_R64R, s, A, (const int4*)w["steps.rows_k3_4"]); });
+            L.run("dec_res64_conv2", [&] { launch_rows<DecR64C2Full>(s, A, w["steps.rows_k3_4"], nt); });
         }
     }
     {
@@ -1591,7 +1604,7 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
             } else if (c->tail_rows32) L.run("dec_tail_rows32", [&] { hipLaunchKernelGGL(tail_rows32_k<0>, dim3((nt + 3) / 4), dim3(256), LDS_TAIL_ROWS, s, A); });
             else L.run("dec_tail", [&] { hipLaunchKernelGGL(tail_rows16_k<0>, dim3((2 * nt + 7) / 8), dim3(512), LDS_TAIL_ROWS, s, A); });
         } else {
-            L.run("dec_tail_slab", [&] { hipLaunchKernelGGL(k_dec_tail, dim3(g8), dim3(512), LDS_DEC_TAIL, s, A, (const int4*)w["steps.tail"]); });
+            L.run("dec_tail_slab", [&] { launch_mfma32<DecTailSlab>(s, A, w["steps.tail"], nt); });
         }
     }
     return L.rc;

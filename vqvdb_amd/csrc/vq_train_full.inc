@@ -163,31 +163,8 @@ int refrag_all(vqhip_codec* c, hipStream_t s)
     return VQHIP_OK;
 }
 
-// kernel instantiations of the training forward / data-gradient convolutions (2-tile workgroups, no fused statistics)
-// The 128-wide layers keep a 64 KB weight window in LDS, i.e. two workgroups per CU: four tiles (waves) per workgroup give two
-// waves per SIMD; the 64 -> 64 layers (32 KB) reach that with two-wave workgroups and a finer position split.
-constexpr auto k_ft_stem = conv_mfma32_k<128, 64, 64, 64, 4, true, 1, 0, 0, false, 0, false, 0>;     // also up_conv^T halves
-constexpr auto k_ft_up = conv_mfma32_k<64, 128, 64, 64, 4, true, 1, 2, 0, false, 0, false, 0>;      // SE gate on load
-constexpr auto k_bt_c64r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 0, false, 0, false, false, 1, false, 8, false, 0, true>;          // res64 conv^T (raw input)
-constexpr auto k_bt_stem = conv_mfma32_k<64, 128, 64, 64, 4, true, 1, 0, 0, false, 0, false, 0>;     // stem^T
-// Round 6: the 64 -> 64 convs of small training batches (up to 2048 leaves) as FOUR cout quarters with LDS-resident weights — inference's
-// choice for such passes (decode_chunk_split).  With one workgroup per (8 half tiles, output row) the launch has exactly as many workgroups as
-// the chip has CUs and a row costs 4, 6 or 9 (kd, kh) steps (corner / edge / interior): the CUs with corner rows idle for half of the kernel
-// (average 6.25 steps against 9: 0.69).  Four times as many workgroups of a quarter of the work each are handed out as CUs free up.
-constexpr auto k_ft_r64c1_s4r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, false, 0, false, true, 4, false, 8, false, 0, true>;
-constexpr auto k_ft_r64c2_s4r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 1, true, 0, false, true, 4, false, 8, false, 0, true>;
-constexpr auto k_bt_c64_s4r = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 0, false, 0, false, true, 4, false, 8, false, 0, true>;
-// ... and for the DATA GRADIENTS, which run beside the weight-gradient kernels (52-76 KB of LDS on every CU): cout quarters / halves with
-// STREAMED weight windows (24 KB / 12 KB of LDS), so that a chain workgroup fits on a CU beside a weight-gradient workgroup.  With 98-110 KB
-// the 32 -> 32 data gradient waited for the stem's weight gradient to leave the CUs: 356 us against 51 us alone
-// (profiles/r06_train_step_timeline_2048_deferred_reductions.txt).
-constexpr auto k_bt_c64_s4 = conv_rows16_k<64, 64, 4, 4, 3, 1, 1, 0, false, 0, false, false, 4, false, 8, false>;
-constexpr auto k_bt_c32_s2 = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 0, false, 0, false, false, 2, false, 8, false>;
-constexpr size_t LDS_BT_C64S4 = (size_t)2 * (3 * 4 * 4 * 64 / 4) * 16, LDS_BT_C32S2 = (size_t)2 * (3 * 2 * 2 * 64 / 2) * 16;
-// folded tail (vq_train_tail.h): data gradient = conv with the 4 output slabs as input positions (128 voxels = channels) and 64 output positions
-constexpr auto k_ft_tail_dgrad = conv_mfma32_k<128, 64, 4, 64, 4, true, 1, 0, 0, false, 0, false, 0>;
-constexpr size_t LDS_FT_STEM = (size_t)2 * (16 * 2 * 64) * 16;
-constexpr size_t LDS_FT_UP = (size_t)2 * (8 * 4 * 64) * 16;
+// the training forward / data-gradient convolutions of the decoder (configurations: vq_kernels.h; 2-tile workgroups, no fused statistics)
+constexpr auto kTrainDecConvs = conv_kernels(TrainDecConvs{});
 
 // folded tail: device tables + static schedules (created once)
 int ensure_tail_tables(vqhip_codec* c)
@@ -230,7 +207,7 @@ int ensure_tail_tables(vqhip_codec* c)
     while (start.size() % 4) start.push_back(start.back());
     if ((rc = upload_i(c, "w.tail", pairs))) return rc;
     if ((rc = upload_i(c, "w.tail.start", start))) return rc;
-    return set_lds(c, k_ft_tail_dgrad, LDS_FT_STEM);
+    return VQHIP_OK;
 }
 
 // "`to` may not pass this point before `from` got here": one event of the per-step pool (c->ft_ev, rewound by the step's entry point)
@@ -384,7 +361,7 @@ int fulltrain_forward(vqhip_codec* c, const float* d_leaves, int64_t n, hipStrea
     } else {
         ConvArgs A{};
         A.in = a["t_q"], A.out = a["d_ystem"], A.wfrag = w["ft.stem.w"], A.bias_frag = w["ft.stem.b"], A.n_tiles = nt, A.n_steps = nk3, A.n_taps = 27, A.grp_start = g64;
-        L.run("ft_stem", [&] { hipLaunchKernelGGL(k_ft_stem, dim3(g4, ps128), dim3(256), LDS_FT_STEM, s, A, k3); });
+        L.run("ft_stem", [&] { launch_mfma32<TrainStem>(s, A, k3, nt, ps128); });
     }
     L.run("ft_stats_ystem", [&] { hipLaunchKernelGGL((gn_stats_seq_k<64, 64, 8>), dim3(nt), dim3(512), 0, s, a["d_ystem"], a["ts_dgn.mean"], a["ts_dgn.rstd"]); });
     L.run("ft_gn_relu_d2", [&] {
@@ -398,15 +375,15 @@ int fulltrain_forward(vqhip_codec* c, const float* d_leaves, int64_t n, hipStrea
         A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27, A.grp_start = gr16;
         const bool q4r = c->train_r64_quarters && gh * psr * 4 <= 1024;   // up to 2048 leaves
         L.run("ft_res64_conv1", [&] {
-            if (q4r) hipLaunchKernelGGL(k_ft_r64c1_s4r, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64S4R, s, A, r3);
-            else hipLaunchKernelGGL(k_dec_r64c1_rs, dim3(gh, psr), dim3(512), LDS_DEC_R64R, s, A, r3);
+            if (q4r) launch_rows<TrainR64C1Split4Res>(s, A, r3, nt, psr);
+            else launch_rows<TrainR64C1>(s, A, r3, nt, psr);
         });
         L.run("ft_stats_y4", [&] { hipLaunchKernelGGL((gn_stats_seq_k<64, 64, 8>), dim3(nt), dim3(512), 0, s, a["d_y4"], a["ts_r64g2.mean"], a["ts_r64g2.rstd"]); });
         A.in = a["d_y4"], A.out = a["d_x6"], A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.skip = a["d_d2"];
         A.in_mean = a["ts_r64g2.mean"], A.in_rstd = a["ts_r64g2.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
         L.run("ft_res64_conv2", [&] {
-            if (q4r) hipLaunchKernelGGL(k_ft_r64c2_s4r, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64S4R, s, A, r3);
-            else hipLaunchKernelGGL(k_dec_r64c2_rs, dim3(gh, psr), dim3(512), LDS_DEC_R64R, s, A, r3);
+            if (q4r) launch_rows<TrainR64C2Split4Res>(s, A, r3, nt, psr);
+            else launch_rows<TrainR64C2>(s, A, r3, nt, psr);
         });
         L.run("ft_csum_x6", [&] { hipLaunchKernelGGL((csum_seq_k<64, 64>), dim3(nt), dim3(512), 0, s, a["d_x6"], a["ts_dcsum"]); });
     }
@@ -427,9 +404,9 @@ int fulltrain_forward(vqhip_codec* c, const float* d_leaves, int64_t n, hipStrea
         ConvArgs A{};
         A.in = a["d_x6"], A.se_csum = a["ts_dcsum"], A.se_fc0 = w["dfc0"], A.se_fc2 = w["dfc2"], A.n_tiles = nt, A.n_steps = nk3, A.n_taps = 27, A.grp_start = g64;
         A.out = a["t_upA"], A.wfrag = w["ft.upA.w"], A.bias_frag = w["ft.upA.b"];
-        L.run("ft_up_conv_a", [&] { hipLaunchKernelGGL(k_ft_up, dim3(g4, ps128), dim3(256), LDS_FT_UP, s, A, k3); });
+        L.run("ft_up_conv_a", [&] { launch_mfma32<TrainUp>(s, A, k3, nt, ps128); });
         A.out = a["t_upB"], A.wfrag = w["ft.upB.w"], A.bias_frag = w["ft.upB.b"];
-        L.run("ft_up_conv_b", [&] { hipLaunchKernelGGL(k_ft_up, dim3(g4, ps128), dim3(256), LDS_FT_UP, s, A, k3); });
+        L.run("ft_up_conv_b", [&] { launch_mfma32<TrainUp>(s, A, k3, nt, ps128); });
     }
     L.run("ft_final", [&] {
         hipLaunchKernelGGL(pixshuf_k<false>, dim3(std::min(nt * 512, 65536)), dim3(256), 0, s, a["t_upA"], a["t_upB"], a["t_ps"], nt);
@@ -801,7 +778,7 @@ int fulltrain_backward_decoder(Bwd& B, int64_t n, float c_mse, float c_l1)
             ConvArgs A{};
             A.in = a["g_pre4"], A.out = a["g64a"], A.wfrag = w["ft.tailT.w"], A.bias_frag = w["bt.zero128"], A.n_tiles = nt;
             A.n_steps = c->nsteps["steps.tailT"], A.n_taps = 224, A.grp_start = reinterpret_cast<const int*>(w["steps.tailT.grp"]);
-            L.run("bt_tail_dgrad", [&] { hipLaunchKernelGGL(k_ft_tail_dgrad, dim3(g4, ps128), dim3(256), LDS_FT_STEM, s, A, (const int4*)w["steps.tailT"]); });
+            L.run("bt_tail_dgrad", [&] { launch_mfma32<DgradTail>(s, A, w["steps.tailT"], nt, ps128); });
         }
         {   // gradient of the folded weights (K = leaves), then the chain rule back to up_conv / final
             WgradArgs A{};
@@ -852,9 +829,9 @@ int fulltrain_backward_decoder(Bwd& B, int64_t n, float c_mse, float c_l1)
             ConvArgs A{};
             A.bias_frag = w["bt.zero128"], A.n_tiles = nt, A.n_steps = nk3, A.n_taps = 27, A.grp_start = g64;
             A.in = a["g_upA"], A.out = a["g64a"], A.wfrag = w["bt.upA.w"];
-            L.run("bt_up_dgrad_a", [&] { hipLaunchKernelGGL(k_ft_stem, dim3(g4, ps128), dim3(256), LDS_FT_STEM, s, A, k3); });
+            L.run("bt_up_dgrad_a", [&] { launch_mfma32<TrainStem>(s, A, k3, nt, ps128); });
             A.in = a["g_upB"], A.out = a["g64b"], A.wfrag = w["bt.upB.w"];
-            L.run("bt_up_dgrad_b", [&] { hipLaunchKernelGGL(k_ft_stem, dim3(g4, ps128), dim3(256), LDS_FT_STEM, s, A, k3); });
+            L.run("bt_up_dgrad_b", [&] { launch_mfma32<TrainStem>(s, A, k3, nt, ps128); });
         }
     }
     {
@@ -882,9 +859,9 @@ int fulltrain_backward_decoder(Bwd& B, int64_t n, float c_mse, float c_l1)
         A.bias_frag = w["bt.zero128"], A.n_tiles = nt, A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27, A.grp_start = gr16;
         A.in = a["g64c"], A.out = a["g64a"], A.wfrag = w["bt.r64c2.w16"];
         L.run("bt_r64c2_dgrad", [&] {
-            if (c->train_r64_quarters && c->train_dgrad_small_lds && gh * psr * 4 <= 1024) hipLaunchKernelGGL(k_bt_c64_s4, dim3(gh, psr, 4), dim3(512), LDS_BT_C64S4, s, A, r3);
-            else if (c->train_r64_quarters && gh * psr * 4 <= 1024) hipLaunchKernelGGL(k_bt_c64_s4r, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64S4R, s, A, r3);
-            else hipLaunchKernelGGL(k_bt_c64r, dim3(gh, psr), dim3(512), LDS_DEC_R64R, s, A, r3);
+            if (c->train_r64_quarters && c->train_dgrad_small_lds && gh * psr * 4 <= 1024) launch_rows<DgradR64Split4>(s, A, r3, nt, psr);
+            else if (c->train_r64_quarters && gh * psr * 4 <= 1024) launch_rows<DgradR64Split4Res>(s, A, r3, nt, psr);
+            else launch_rows<DgradR64>(s, A, r3, nt, psr);
         });
     }
     B.gn_bwd<64, 64, 8>("bt_r64gn2", a["d_y4"], a["g64a"], "ts_r64g2", "decoder.res_stack.0.gn2.weight", "decoder.res_stack.0.gn2.bias", nullptr, a["g64b"]);
@@ -896,9 +873,9 @@ int fulltrain_backward_decoder(Bwd& B, int64_t n, float c_mse, float c_l1)
         A.bias_frag = w["bt.zero128"], A.n_tiles = nt, A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27, A.grp_start = gr16;
         A.in = a["g64b"], A.out = a["g64a"], A.wfrag = w["bt.r64c1.w16"];
         L.run("bt_r64c1_dgrad", [&] {
-            if (c->train_r64_quarters && c->train_dgrad_small_lds && gh * psr * 4 <= 1024) hipLaunchKernelGGL(k_bt_c64_s4, dim3(gh, psr, 4), dim3(512), LDS_BT_C64S4, s, A, r3);
-            else if (c->train_r64_quarters && gh * psr * 4 <= 1024) hipLaunchKernelGGL(k_bt_c64_s4r, dim3(gh, psr, 4), dim3(512), LDS_DEC_R64S4R, s, A, r3);
-            else hipLaunchKernelGGL(k_bt_c64r, dim3(gh, psr), dim3(512), LDS_DEC_R64R, s, A, r3);
+            if (c->train_r64_quarters && c->train_dgrad_small_lds && gh * psr * 4 <= 1024) launch_rows<DgradR64Split4>(s, A, r3, nt, psr);
+            else if (c->train_r64_quarters && gh * psr * 4 <= 1024) launch_rows<DgradR64Split4Res>(s, A, r3, nt, psr);
+            else launch_rows<DgradR64>(s, A, r3, nt, psr);
         });
     }
     // (into g64d: the side stream may still be reading g64b for conv1's weight gradient)
@@ -911,14 +888,12 @@ int fulltrain_backward_decoder(Bwd& B, int64_t n, float c_mse, float c_l1)
         ConvArgs A{};
         A.bias_frag = w["bt.zero128"], A.n_tiles = nt, A.n_steps = nk3, A.n_taps = 27, A.grp_start = g64;
         A.in = a["g64a"], A.out = a["g_q"], A.wfrag = w["bt.stem.w"];
-        L.run("bt_stem_dgrad", [&] { hipLaunchKernelGGL(k_bt_stem, dim3(g4, ps128), dim3(256), LDS_FT_UP, s, A, k3); });
+        L.run("bt_stem_dgrad", [&] { launch_mfma32<DgradStem>(s, A, k3, nt, ps128); });
     }
     return L.rc;
 }
 
-constexpr auto k_bt_proj = conv_mfma32_k<128, 32, 64, 64, 2, true, 1, 0, 0, false, 0, false, 0>;                // proj^T (one tap)
-constexpr auto k_bt_c32r = conv_rows16_k<32, 32, 4, 4, 3, 1, 1, 0, false, 0, false, true, 1, false, 8, false, 0, true>;                         // res32 conv^T (raw input, resident weights)
-constexpr size_t LDS_BT_PROJ = (size_t)2 * (16 * 1 * 64) * 16;
+constexpr auto kTrainEncConvs = conv_kernels(TrainEncConvs{});   // ... and of the encoder: proj^T, res32 conv^T
 
 // backward of the quantizer's straight-through path and of the encoder: consumes d(loss)/d(q) in "g_q"
 int fulltrain_backward_encoder(Bwd& B, int64_t n, float c_commit)
@@ -939,7 +914,7 @@ int fulltrain_backward_encoder(Bwd& B, int64_t n, float c_commit)
         A.bias_frag = w["bt.zero128"], A.n_tiles = nt, A.n_steps = c->nsteps["steps.k1_4"], A.n_taps = 1;
         A.grp_start = reinterpret_cast<const int*>(w["steps.k1_4.grp"]);
         A.in = a["g_q"], A.out = a["g32a"], A.wfrag = w["bt.proj.w"];
-        L.run("bt_proj_dgrad", [&] { hipLaunchKernelGGL(k_bt_proj, dim3(g2, split_factor(g2, 1, 16, 1024)), dim3(128), LDS_BT_PROJ, s, A, (const int4*)w["steps.k1_4"]); });
+        L.run("bt_proj_dgrad", [&] { launch_mfma32<DgradProj>(s, A, w["steps.k1_4"], nt, split_factor(g2, 1, 16, 1024)); });
     }
     {
         // (its own region of the small partials: the decoder's attention reduction may still be pending on the reduction stream)
@@ -970,8 +945,8 @@ int fulltrain_backward_encoder(Bwd& B, int64_t n, float c_commit)
         A.in = a["g32b"], A.out = a["g32a"], A.wfrag = w["bt.r32c2.w16"];
         L.run("bt_r32c2_dgrad", [&] {
             const int ps32 = split_factor(gh32, 1, 16, 512);
-            if (c->train_dgrad_small_lds && gh32 * ps32 * 2 <= 1024) hipLaunchKernelGGL(k_bt_c32_s2, dim3(gh32, ps32, 2), dim3(512), LDS_BT_C32S2, s, A, r3);
-            else hipLaunchKernelGGL(k_bt_c32r, dim3(gh32, ps32), dim3(512), LDS_ENC_R32R, s, A, r3);
+            if (c->train_dgrad_small_lds && gh32 * ps32 * 2 <= 1024) launch_rows<DgradR32Split2>(s, A, r3, nt, ps32);
+            else launch_rows<DgradR32>(s, A, r3, nt, ps32);
         });
     }
     B.gn_bwd<32, 64, 4>("bt_r32gn2", a["e_y9"], a["g32a"], "ts_r32g2", "encoder.res_stack.0.gn2.weight", "encoder.res_stack.0.gn2.bias", nullptr, a["g32c"]);
@@ -984,8 +959,8 @@ int fulltrain_backward_encoder(Bwd& B, int64_t n, float c_commit)
         A.in = a["g32c"], A.out = a["g32a"], A.wfrag = w["bt.r32c1.w16"];
         L.run("bt_r32c1_dgrad", [&] {
             const int ps32 = split_factor(gh32, 1, 16, 512);
-            if (c->train_dgrad_small_lds && gh32 * ps32 * 2 <= 1024) hipLaunchKernelGGL(k_bt_c32_s2, dim3(gh32, ps32, 2), dim3(512), LDS_BT_C32S2, s, A, r3);
-            else hipLaunchKernelGGL(k_bt_c32r, dim3(gh32, ps32), dim3(512), LDS_ENC_R32R, s, A, r3);
+            if (c->train_dgrad_small_lds && gh32 * ps32 * 2 <= 1024) launch_rows<DgradR32Split2>(s, A, r3, nt, ps32);
+            else launch_rows<DgradR32>(s, A, r3, nt, ps32);
         });
     }
     // (into g32d: the side stream may still be reading g32c for conv1's weight gradient)
@@ -1053,11 +1028,7 @@ int vqhip_fulltrain_begin(vqhip_codec* c)
     HIPCHK(c, hipMemset(c->ft_V, 0, np * sizeof(float)));
     if ((rc = refrag_all(c, c->stream))) return rc;
     if (!c->dw.count("steps.k1_4") && (rc = upload_steps(c, "steps.k1_4", steps_conv(4, 4, 1, 1, 0, 1)))) return rc;
-    if ((rc = set_lds(c, k_bt_c32r, LDS_ENC_R32R))) return rc;
-    if ((rc = set_lds(c, k_bt_c64r, LDS_DEC_R64R))) return rc;
-    if ((rc = set_lds(c, k_ft_r64c1_s4r, LDS_DEC_R64S4R))) return rc;
-    if ((rc = set_lds(c, k_ft_r64c2_s4r, LDS_DEC_R64S4R))) return rc;
-    if ((rc = set_lds(c, k_bt_c64_s4r, LDS_DEC_R64S4R))) return rc;
+    if ((rc = set_lds(c, kTrainDecConvs)) || (rc = set_lds(c, kTrainEncConvs))) return rc;
     if ((rc = upload_wsteps(c, "w.k3_4", 4, 4, 3, 1, 1))) return rc;
     if ((rc = upload_wsteps(c, "w.k3_8", 8, 8, 3, 1, 1))) return rc;
     if ((rc = upload_wsteps(c, "w.k4s2", 8, 4, 4, 2, 1))) return rc;
