@@ -1,6 +1,6 @@
 """bf16 decode mode of the scalar handle on the GPU: the default path unchanged, error handling, the two convs
 teacher-forced against tests/torch_ref_precision.py, bit invariance over batch size / place / chunk / launch path / stream /
-entry point, closeness to fp32 mode end to end, the fragments after training, and the file call."""
+entry point, one handle alternating modes and sizes, closeness to fp32 mode end to end, the fragments after training, and the file call."""
 import os
 import sys
 
@@ -147,11 +147,31 @@ def test_both_convs_teacher_forced_against_the_bf16_restatement(codec, weights, 
     assert not over, f"tensors outside the flip cap (name, share over 1e-5, largest error / largest value): {over}"
 
 
-@pytest.mark.parametrize("n", [1, 17, 33])
+@pytest.mark.parametrize("n", [1, 17, 33, 15, 16, 31, 32, 48, 49, 64, 65])
 def test_a_prefix_decoded_alone_has_the_same_bits(pack, pair, bf16_97, n):
+    """A workgroup serves a half tile of 16 leaves (grid = 2 * n_tiles): either side of every half-tile and tile edge up to 65."""
     c = HipCodec(pack, decode_precision="bf16")
     try:
         assert np.array_equal(bits(c.decode(pair[1][:n])), bits(bf16_97[:n]))
+    finally:
+        c.close()
+
+
+def test_one_handle_alternating_modes_and_sizes(pack, pair):
+    """fp32 with 33 leaves, bf16 with 97, fp32 with 1, bf16 with 17, bf16 with 65 on ONE handle (the workspace, the statistics
+    partials and the fragments are shared between the modes): each result has the bits of a fresh handle in the same mode."""
+    idx = pair[1]
+    c = HipCodec(pack)
+    try:
+        for mode, n in (("fp32", 33), ("bf16", 97), ("fp32", 1), ("bf16", 17), ("bf16", 65)):
+            c.decode_precision = mode
+            got = c.decode(idx[:n])
+            fresh = HipCodec(pack, decode_precision=mode)
+            try:
+                want = fresh.decode(idx[:n])
+            finally:
+                fresh.close()
+            assert np.array_equal(bits(got), bits(want)), (mode, n)
     finally:
         c.close()
 
