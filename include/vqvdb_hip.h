@@ -23,6 +23,9 @@
  * the slab kernel (VQHIP_TAIL=slab) and the oracle's skip_rows = 0 form compute 0 x Inf = NaN there.  For finite activations all
  * forms are bit-identical; tests/test_gpu_parity.py::test_large_path_kernel_variants_agree pins that.)
  *
+ * Kernel switches (VQHIP_TAIL and the others: the table "Kernel switches" of INTEGRATION.md) are environment variables read once at
+ * vqhip_create; unknown or out-of-range values make vqhip_create fail with VQHIP_ERR_INVALID.
+ *
  * Every function returns VQHIP_OK (0) or a negative status; the message is available from
  * vqhip_last_error().  Nothing throws, nothing aborts.  A codec handle owns its device
  * buffers and streams; distinct handles may be used from distinct threads concurrently,
@@ -139,7 +142,8 @@ int vqhip_compress_file(vqhip_codec* codec, const char* path, const vqhip_grid_s
  * and writes to the same offsets of the caller's buffer.  Weights are replicated; there is no collective.
  * The host threads are persistent (created here, asleep between calls); each is bound to the cores of its GPU's NUMA
  * node when /sys exposes it (pinned staging is then allocated node-local), and all devices together fan out to at
- * most min(cores, 64) copy threads (override per thread with the environment variable VQHIP_COPY_THREADS).
+ * most min(cores, 64) copy threads (override per thread with the environment variable VQHIP_COPY_THREADS; unknown or out-of-range values make vqhip_create fail with VQHIP_ERR_INVALID,
+ * here through the handles that vqhip_multi_create creates).
  * (Process-per-GPU callers use one plain codec per rank instead: bench.py, vqvdb_amd/sharding.py.) */
 typedef struct vqhip_multi vqhip_multi;
 int vqhip_multi_create(const char* pack_path, const void* pack_bytes, size_t pack_size, const int* device_ids, int n_devices, vqhip_multi** out);
@@ -178,7 +182,7 @@ int64_t vqhip_workspace_bytes(const vqhip_codec* codec);
 int64_t vqhip_chunk_leaves(const vqhip_codec* codec);
 /* Compute units: *device is the device's own count, *in_use the count the persistent-workgroup grids, the weight-gradient
  * slices and the launch policies are derived from.  They differ only under VQHIP_CUS=k (1 <= k <= *device, read at create;
- * anything else makes vqhip_create fail with VQHIP_ERR_INVALID): the launch geometry of a device with k compute units, for
+ * unknown or out-of-range values make vqhip_create fail with VQHIP_ERR_INVALID): the launch geometry of a device with k compute units, for
  * tests and for parts that report fewer.  It takes no compute unit away from the device and results never depend on it (the weight
  * gradients' order of partial sums does).  Either pointer may be NULL. */
 int vqhip_compute_units(const vqhip_codec* codec, int* device, int* in_use);

@@ -32,6 +32,7 @@
 #include "../../include/vqvdb_hip_residual.h"
 #include "../../include/vqvdb_hip_precision.h"
 #include "vq_buffers.h"
+#include "vq_switches.h"
 #include "vq_kernels.h"
 #include "vq_conv8_lds.h"
 #include "vq_stem_taps.h"
@@ -182,32 +183,13 @@ const std::map<std::string, KernelInfo>& kernel_info()
 
 }  // namespace
 
-struct vqhip_codec {
+struct vqhip_codec : Switches {   // the switch-controlled fields (n_cus, conv8_lds, train_* ...): vq_switches.h
     int device = 0;
     std::string err;
     hipStream_t stream = nullptr;
     int64_t chunk = 65536;
-    int n_cus = 256;         // compute units the persistent-workgroup launches, the weight-gradient slices and the launch policies count on: the device's, or fewer (VQHIP_CUS)
     int n_cus_device = 256;  // compute units of the device itself (CU mask of the reduction stream)
-    bool stem_fused = true;  // decoder front of large passes: one kernel; VQHIP_STEM=split selects stem_lut_k + gn_relu_stats_k
-    bool stem_taps = true;   // ... the (tap, code) table streamed through an LDS ring tap by tap (stem_taps_k, vq_stem_taps.h: 0.81 -> 0.57 ms); VQHIP_STEM=gather selects stem_fused_k (gather through the L1)
-    bool tail_groups = false; // ... VQHIP_TAIL=groups: the output planes in three groups instead of five units, every input plane read 2.5x instead of 3.5x (tail_groups16_k, vq_tail_groups.h; measured equal in time, 33 spilled registers)
-    bool tail_rows32 = false; // ... VQHIP_TAIL=rows32: a whole 32-leaf tile per wave, one wave per SIMD (tail_rows32_k; measured 4 % slower)
-    bool tail_rows = true;   // folded decoder tail of full chunks: 16-voxel tiles, zeros skipped along D and H (tail_rows16_k, vq_tail_rows.h); VQHIP_TAIL=slab selects conv_mfma32_k<OUTMODE 2> (depth only)
-    int host_split = 8;      // host-memory calls of one chunk are cut into up to host_split pieces of >= host_split_min leaves (VQHIP_HOST_SPLIT=n[,min]; 1 = off)
-    int64_t host_split_min = 8192;
-    int tail16_tiles = 48;   // small-batch folded tail on the 16x16x4 MFMA up to this many tiles (VQHIP_TAIL16_TILES; measured: 1024 leaves 90 -> 56 us, 2048 leaves 92 -> 103 us)
-    bool r64s_resident = true;   // small-batch 64->64 convs: their quarter of the weights LDS-resident (VQHIP_R64S=stream: streamed)
-    int vq_split = 2;        // position ranges per tile in the VQ search of full chunks (VQHIP_VQ_SPLIT)
-    bool conv8_w16 = true;   // ... with 16 waves (one half row each; a half row is a statistics block); VQHIP_CONV8=w8 selects 8 (one row each)
-    bool convdown_lds = true;   // down conv of large passes: input planes streamed through LDS once, weights from L1 / L2 (vq_convdown_lds.h); VQHIP_DOWN=rows selects the row kernel (input re-fetched 3.06x)
-    bool conv4_lds = true;   // 32-channel 4^3 convs of large passes: input planes in an LDS ring, weights straight from L1 / L2 (vq_conv4_lds.h); VQHIP_CONV4=rows selects the row kernel (weights LDS-resident, every input row re-fetched 6.25x)
-    bool first_once = true;  // first conv of full chunks issued once, an 8-leaf group's output held in the accumulators of one workgroup (conv_first_once_k, vq_first_once.h); VQHIP_FIRST=twopass|steps|roll0 and VQHIP_FIRST_SRC=raw select the two-pass sequence below
-    bool first_roll_stats = false;   // ... for the statistics pass too (VQHIP_FIRST=roll0; measured slower)
-    bool first_raw = false;  // VQHIP_FIRST_SRC=raw: the first conv reads the caller's float[leaf][512] layout itself and pack_leaves_k is not launched (round 6; measured SLOWER: 0.425 + 0.465 ms against 0.069 + 0.322 + 0.396 ms with the row layout — 16 cache lines per load instead of 6)
     const float* cur_leaves = nullptr;   // the current pass's input leaves (device), for the split path's first conv
-    bool first_roll = true;  // first conv of large passes, normalising pass: rolling row window in registers (vq_first_roll.h); VQHIP_FIRST=steps selects conv_first_k ((row, kd) steps, nine row loads per output row)
-    bool conv8_lds = true;   // 16-channel 8^3 convs of large passes: LDS-plane kernel (vq_conv8_lds.h); VQHIP_CONV8=rows selects the row-group kernel
     int split_tiles = -1;    // position-split path: -1 = automatic (measured crossovers, use_split), >= 0 = plain tile threshold
 
     // device weights
@@ -254,26 +236,12 @@ struct vqhip_codec {
     int64_t ft_tiles = 0;                                          // ... laid out for this many tiles
     DevBuf<char> ft_part;                                          // partial-gradient scratch
     bool full_training = false, keep_y1 = false, weights_stale = false;
-    bool train_gn_fused = true;      // GroupNorm + ReLU backward as one pass per layer (gn_bwd_fused_k); VQHIP_TRAIN_GNBWD=split: sums + finish + apply
-    bool train_bias_main = true;     // bias gradients on the data-gradient stream when there is no reduction stream (VQHIP_TRAIN_BIAS=side: beside the weight gradients)
-    bool train_red_stream = false;   // round 6, first attempt: bias sums, GroupNorm-affine / attention-weight reductions on a third stream (VQHIP_TRAIN_BIAS=third; fast or slow depending on the hardware queue the stream lands on)
-    bool train_red_deferred = true;  // round 6: ... as two multi-job launches at the end of the data-gradient chain (csum_multi_k, reduce_multi_k); VQHIP_TRAIN_BIAS=main|side|third: the other arrangements
-    bool train_ema_early = true;     // round 6: the codebook statistics start on the side stream as soon as the assignment exists, beside the decoder's forward (VQHIP_TRAIN_EMA_AT=backward: with the backward pass)
-    bool train_side_stream = true;   // training backward: weight / bias gradients on a second stream beside the data-gradient chain (VQHIP_TRAIN_STREAMS=1: one stream)
     hipStream_t ft_side = nullptr;
     hipStream_t ft_red_shared = nullptr;   // ... the same on a plain stream (shares a hardware queue with the weight-gradient stream): large batches
-    int64_t train_red_own_leaves = 2048;   // batches up to this size use ft_red (VQHIP_TRAIN_RED_OWN_LEAVES)
-    bool train_r64_quarters = true;        // 64 -> 64 convs of small training batches in four cout quarters with resident weights (VQHIP_TRAIN_R64=whole: one workgroup per row)
-    bool train_dgrad_small_lds = true;     // data gradients of the 4^3 layers with streamed weight windows (VQHIP_TRAIN_DGRAD=resident: LDS-resident weights)
-    int train_wgrad_cu_pct = 100;          // wgrad_rows4_k: slices as a percentage of one-per-CU (VQHIP_TRAIN_WGRAD_CU_PCT)
     bool ft_egate_early = false;           // this step's encoder attention gates were computed beside the forward pass
     hipStream_t ft_red = nullptr;    // third stream of the training step (round 6): the small reductions nothing on the data-gradient chain waits for (bias sums, GroupNorm-affine and attention-weight reductions)
     std::vector<hipEvent_t> ft_ev;   // fork / join events of the side stream, reused every step
     size_t ft_ev_next = 0;
-    bool train_wgrad_rows = true;    // training backward: weight gradients of the k3 layers at 4^3 by wgrad_rows4_k (VQHIP_TRAIN_WGRAD=pairs: wgrad32_k)
-    bool train_stem_lut = true;      // training forward: decoder stem through the (tap, code) table rebuilt every step (VQHIP_TRAIN_STEM=conv: the real conv)
-    bool train_ema_lists = true;     // codebook statistics from per-(segment, code) member lists (vq_ema_lists_k + vq_ema_gather_k); VQHIP_TRAIN_EMA=scan: every (code, segment) wave scans the indices
-    bool train_folded_tail = true;   // training step: up_conv + PixelShuffle3D + final as one folded operator (vq_train_tail.h); VQHIP_TRAIN_TAIL=unfolded keeps the layer-by-layer tail
     float* z4_out = nullptr;   // set around encode_chunk by the training forward: latent also in the L4 layout
     DevBuf<char> tr_part;      // per-(code, row segment) partial statistics
     DevBuf<float> tr_recon;    // reconstruction scratch of vqhip_train_eval_device
@@ -1464,7 +1432,7 @@ int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_
         F.out_mean = a["st_b.mean"], F.out_rstd = a["st_b.rstd"], F.ystem_dbg = c->debug ? a["d_ystem"] : nullptr;
         F.n_leaves = n, F.n_tiles = nt;
         L.run("dec_stem_gn_s", [&] { hipLaunchKernelGGL(k_stem_taps, dim3(std::min(nt, c->n_cus)), dim3(512), LDS_STEM_TAPS, s, F); });
-    } else if (c->stem_fused && getenv("VQHIP_STEM_SMALL") == nullptr) {
+    } else if (c->stem_fused && c->stem_small_fused) {
         // SOP-sized passes: the decoder front as ONE kernel too — a workgroup per four leaves gathers its table rows through the L1,
         // normalises out of LDS and finishes both sets of statistics itself (stem_fused_k) — instead of gather + combine + normalise +
         // combine (four launches of 6-23 us each at 64 leaves); same d2 and statistics bit for bit
@@ -1644,9 +1612,12 @@ thread_local int g_copy_threads_cap = 16;
 
 int copy_threads_cap()
 {
-    static const int env = [] {
-        const char* e = std::getenv("VQHIP_COPY_THREADS");
-        return e ? std::max(1, std::atoi(e)) : 0;
+    static const int env = [] {   // (the switch table's strict integer: a malformed value means "not set" here and refuses every vqhip_create)
+        long v[2];
+        int n = 0;
+        std::string err;
+        const bool ok = vqsw::parse_switch_integers(*vqsw::find_switch("VQHIP_COPY_THREADS"), std::getenv("VQHIP_COPY_THREADS"), 0, v, n, err) == VQHIP_OK;
+        return ok && n ? (int)v[0] : 0;
     }();
     return env ? env : g_copy_threads_cap;
 }
@@ -1925,53 +1896,9 @@ int vqhip_create(const char* pack_path, const void* pack_bytes, size_t pack_size
         c->err = std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only";
         return bail(VQHIP_ERR_DEVICE);
     }
-    c->n_cus = c->n_cus_device = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (const char* e = std::getenv("VQHIP_CUS")) {   // launch geometry as on a device with fewer compute units; masks no compute unit off
-        char* end = nullptr;
-        errno = 0;
-        const long k = std::strtol(e, &end, 10);
-        if (!*e || *end || errno || k < 1 || k > c->n_cus_device) {
-            c->err = std::string("VQHIP_CUS=") + e + ": not an integer in [1, " + std::to_string(c->n_cus_device) + "] (the device's compute units)";
-            return bail(VQHIP_ERR_INVALID);
-        }
-        c->n_cus = (int)k;
-    }
-    if (const char* e = std::getenv("VQHIP_DOWN")) c->convdown_lds = std::strcmp(e, "rows") != 0;
-    if (const char* e = std::getenv("VQHIP_CONV4")) c->conv4_lds = std::strcmp(e, "rows") != 0;
-    if (const char* e = std::getenv("VQHIP_FIRST_SRC")) c->first_raw = std::strcmp(e, "raw") == 0;
-    if (const char* e = std::getenv("VQHIP_FIRST")) {   // twopass | steps | roll0: the two-pass sequence (with its default kernels / conv_first_k for both passes / the row window for both)
-        c->first_once = std::strcmp(e, "twopass") != 0 && std::strcmp(e, "steps") != 0 && std::strcmp(e, "roll0") != 0;
-        c->first_roll = std::strcmp(e, "steps") != 0, c->first_roll_stats = std::strcmp(e, "roll0") == 0;
-    }
-    if (const char* e = std::getenv("VQHIP_CONV8")) c->conv8_lds = std::strcmp(e, "rows") != 0, c->conv8_w16 = std::strcmp(e, "w8") != 0;
-    if (const char* e = std::getenv("VQHIP_TAIL16_TILES")) c->tail16_tiles = std::atoi(e);
-    if (const char* e = std::getenv("VQHIP_HOST_SPLIT")) {
-        c->host_split = std::max(1, std::atoi(e));
-        if (const char* m = std::strchr(e, ',')) c->host_split_min = std::max(32, std::atoi(m + 1));
-    }
-    if (const char* e = std::getenv("VQHIP_TAIL")) {
-        if (std::strcmp(e, "rows16") && std::strcmp(e, "slab") && std::strcmp(e, "rows32") && std::strcmp(e, "groups") && *e) {
-            c->err = std::string("VQHIP_TAIL=") + e + ": unknown folded-tail variant (rows16 | rows32 | groups | slab)";
-            return bail(VQHIP_ERR_INVALID);
-        }
-        c->tail_rows = std::strcmp(e, "slab") != 0, c->tail_rows32 = std::strcmp(e, "rows32") == 0, c->tail_groups = std::strcmp(e, "groups") == 0;
-    }
-    if (const char* e = std::getenv("VQHIP_R64S")) c->r64s_resident = std::strcmp(e, "stream") != 0;
-    if (const char* e = std::getenv("VQHIP_VQ_SPLIT")) c->vq_split = std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("VQHIP_TRAIN_STEM")) c->train_stem_lut = std::strcmp(e, "conv") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_WGRAD")) c->train_wgrad_rows = std::strcmp(e, "pairs") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_STREAMS")) c->train_side_stream = std::strcmp(e, "1") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_GNBWD")) c->train_gn_fused = std::strcmp(e, "split") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_BIAS"))
-        c->train_bias_main = std::strcmp(e, "side") != 0, c->train_red_stream = std::strcmp(e, "third") == 0, c->train_red_deferred = std::strcmp(e, "deferred") == 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_R64")) c->train_r64_quarters = std::strcmp(e, "whole") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_DGRAD")) c->train_dgrad_small_lds = std::strcmp(e, "resident") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_WGRAD_CU_PCT")) c->train_wgrad_cu_pct = std::min(100, std::max(10, std::atoi(e)));
-    if (const char* e = std::getenv("VQHIP_TRAIN_RED_OWN_LEAVES")) c->train_red_own_leaves = std::atoll(e);
-    if (const char* e = std::getenv("VQHIP_TRAIN_EMA_AT")) c->train_ema_early = std::strcmp(e, "backward") != 0;
-    if (const char* e = std::getenv("VQHIP_STEM")) c->stem_fused = std::strcmp(e, "split") != 0, c->stem_taps = std::strcmp(e, "gather") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_TAIL")) c->train_folded_tail = std::strcmp(e, "unfolded") != 0;
-    if (const char* e = std::getenv("VQHIP_TRAIN_EMA")) c->train_ema_lists = std::strcmp(e, "scan") != 0;
+    c->n_cus_device = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    // every VQHIP_* switch, read here and nowhere later (vq_switches.h: the table, the legal values, what each selects)
+    if (int rc = parse_switches(*c, [](const char* name) -> const char* { return std::getenv(name); }, c->n_cus_device, c->err)) return bail(rc);
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         c->err = "hipStreamCreate failed";
         return bail(VQHIP_ERR_DEVICE);

@@ -232,9 +232,8 @@ int side_stream(vqhip_codec* c, hipStream_t s, hipStream_t& ws)
     if (!c->ft_side) {
         // VQHIP_TRAIN_SIDE_PRIO=high|low: the weight-gradient stream's queue priority against the data-gradient stream (the caller's)
         int lo = 0, hi = 0;
-        const char* pe = std::getenv("VQHIP_TRAIN_SIDE_PRIO");
-        if (pe && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
-            HIPCHK(c, hipStreamCreateWithPriority(&c->ft_side, hipStreamNonBlocking, std::strcmp(pe, "high") == 0 ? hi : lo));
+        if (c->train_side_prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
+            HIPCHK(c, hipStreamCreateWithPriority(&c->ft_side, hipStreamNonBlocking, c->train_side_prio > 0 ? hi : lo));
         else HIPCHK(c, hipStreamCreateWithFlags(&c->ft_side, hipStreamNonBlocking));
     }
     ws = c->ft_side;
@@ -248,9 +247,8 @@ int side_stream(vqhip_codec* c, hipStream_t s, hipStream_t& ws)
         // VQHIP_TRAIN_RED_QUEUE=mask (default): a stream created with a CU mask owns its HSA queue (the mask is a queue property) — a full mask
         // gives a dedicated queue at NORMAL priority; =prio: a high-priority stream (round 6's first attempt: a dedicated queue too, but
         // erratic — 4.87 ms against 2.70 at 1024 leaves per rank, 9.4 against 7.2 at 4096, equal at 2048)
-        const char* qe = std::getenv("VQHIP_TRAIN_RED_QUEUE");
         int lo = 0, hi = 0;
-        if (qe && std::strcmp(qe, "prio") == 0 && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
+        if (!c->train_red_queue_mask && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
             HIPCHK(c, hipStreamCreateWithPriority(&c->ft_red, hipStreamNonBlocking, hi));
         } else {
             std::vector<uint32_t> mask((size_t)(c->n_cus_device + 31) / 32, 0xffffffffu);   // the device's own count: VQHIP_CUS masks nothing off
@@ -1086,8 +1084,7 @@ int vqhip_fulltrain_fwdbwd_overlap_device(vqhip_codec* c, const float* d_leaves,
     if ((rc = side_stream(c, s, B.ws))) return rc;
     B.rs = s;
     if (B.ws != s && c->train_red_stream && !c->train_red_deferred && c->ft_red) {
-        const char* pe = std::getenv("VQHIP_TRAIN_RED_PRIO");
-        const bool own = pe ? std::strcmp(pe, "own") == 0 || (std::strcmp(pe, "normal") != 0 && n <= c->train_red_own_leaves) : n <= c->train_red_own_leaves;
+        const bool own = c->train_red_prio ? c->train_red_prio > 0 : n <= c->train_red_own_leaves;
         B.rs = own ? c->ft_red : c->ft_red_shared;
     }
     HIPCHK(c, hipMemsetAsync(d_grads, 0, c->h_params.size() * sizeof(float), s));
