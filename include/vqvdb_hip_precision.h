@@ -14,8 +14,8 @@
  *
  * Calls that ignore it and always run the fp32 decoder: every call that states or checks an error bound against the fp32
  * reconstruction and stores no mode in its records (vqhip_roundtrip_device, the *_bounded and *_residual* calls, the size sweep
- * of vqvdb_hip_rate.h, and their file forms), both training families (vqhip_train_*, vqhip_fulltrain_*) and vqhip_multi_*.  Encoding has one
- * precision.  After a training update (vqhip_train_commit, vqhip_fulltrain_apply_device, _set_params, _set_state) the next
+ * of vqvdb_hip_rate.h, and their file forms), both training families (vqhip_train_*, vqhip_fulltrain_*) and vqhip_multi_*.  Encoding has a
+ * mode of its own, independent of this one: vqvdb_hip_encode_mode.h.  After a training update (vqhip_train_commit, vqhip_fulltrain_apply_device, _set_params, _set_state) the next
  * bf16 decode packs its weight fragments again from the live parameters: they equal those of a fresh handle built from the
  * exported pack.
  *

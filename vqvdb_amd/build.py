@@ -18,6 +18,7 @@ DEPS = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HER
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_fulltrain.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_precision.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_precision.h"),
+    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_encode_mode.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_bounded.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_bounded.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_residual.h"),

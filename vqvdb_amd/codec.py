@@ -122,6 +122,8 @@ VEC3_PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_VEC3_PRECISION_*
 # every symbol include/vqvdb_hip_precision.h declares (decode precision mode of the scalar handle; kept apart from the lists above)
 PRECISION_SYMBOLS = ["vqhip_set_decode_mode", "vqhip_get_decode_mode"]
 PRECISIONS = {"fp32": 0, "bf16": 1}   # VQHIP_PRECISION_*
+# every symbol include/vqvdb_hip_encode_mode.h declares (encode operand mode of the scalar handle; the values are PRECISIONS)
+ENCODE_MODE_SYMBOLS = ["vqhip_set_encode_mode", "vqhip_get_encode_mode"]
 # every symbol include/vqvdb_hip_vec3_bounded.h declares (Vec3 error-bounded round trip; kept apart from the lists above)
 VEC3_BOUNDED_SYMBOLS = ["vqhip_vec3_roundtrip_device", "vqhip_vec3_select_outliers_device", "vqhip_vec3_compress_bounded"]
 VEC3_ERR_FLOATS = 2   # VQHIP_VEC3_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
@@ -313,6 +315,11 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_set_decode_mode.argtypes = [vp, ci]
     lib.vqhip_get_decode_mode.argtypes = [vp, vp]
     for name in PRECISION_SYMBOLS:
+        getattr(lib, name).restype = ci
+    # include/vqvdb_hip_encode_mode.h
+    lib.vqhip_set_encode_mode.argtypes = [vp, ci]
+    lib.vqhip_get_encode_mode.argtypes = [vp, vp]
+    for name in ENCODE_MODE_SYMBOLS:
         getattr(lib, name).restype = ci
     # include/vqvdb_hip_vec3_bounded.h
     lib.vqhip_vec3_roundtrip_device.argtypes = [vp, vp, i64, vp, vp, vp, vp]
@@ -952,8 +959,10 @@ class HipVec3Codec:
 class HipCodec:
     """Thin owner of a ``vqhip_codec*`` — the C ABI one-to-one, numpy/raw pointers in and out."""
 
-    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0, decode_precision: str = "fp32"):
+    def __init__(self, pack: Union[str, os.PathLike, bytes], device_id: int = 0, decode_precision: str = "fp32",
+                 encode_precision: str = "fp32"):
         self.check_decode_precision(decode_precision)
+        self.check_encode_precision(encode_precision)
         self._lib = load_library()
         self._h = ctypes.c_void_p()
         if isinstance(pack, (bytes, bytearray, memoryview)):
@@ -965,6 +974,8 @@ class HipCodec:
             raise RuntimeError(self._lib.vqhip_last_error(None).decode())
         if decode_precision != "fp32":
             self.decode_precision = decode_precision
+        if encode_precision != "fp32":
+            self.encode_precision = encode_precision
 
     @staticmethod
     def check_decode_precision(precision) -> int:
@@ -985,6 +996,26 @@ class HipCodec:
     @decode_precision.setter
     def decode_precision(self, precision: str):
         self._check(self._lib.vqhip_set_decode_mode(self._h, self.check_decode_precision(precision)))
+
+    @staticmethod
+    def check_encode_precision(precision) -> int:
+        """"fp32" / "bf16" -> VQHIP_PRECISION_* (include/vqvdb_hip_encode_mode.h)."""
+        if not isinstance(precision, str) or precision not in PRECISIONS:
+            raise ValueError(f"encode_precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
+        return PRECISIONS[precision]
+
+    @property
+    def encode_precision(self) -> str:
+        """Operand precision of the encoder's two 16-channel convs in encode / encode_device / encode_leaves / compress_file and
+        the debug_fetch after them: "fp32" (default) or "bf16" (DESIGN §24).  Every bounded, residual, rate, round-trip and
+        training call encodes in fp32 whatever this says, and decode_precision is a separate switch."""
+        mode = ctypes.c_int(-1)
+        self._check(self._lib.vqhip_get_encode_mode(self._h, ctypes.byref(mode)))
+        return {v: k for k, v in PRECISIONS.items()}[mode.value]
+
+    @encode_precision.setter
+    def encode_precision(self, precision: str):
+        self._check(self._lib.vqhip_set_encode_mode(self._h, self.check_encode_precision(precision)))
 
     def _check(self, rc: int):
         if rc != 0:

@@ -384,7 +384,9 @@ int compress_file_impl(vqhip_codec* c, const char* path, const char* residual_pa
                 if (side.failed) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
                 return wfail ? fail(c, VQHIP_ERR_INVALID, "Failed to write to .vqvdb file.") : VQHIP_OK;
             },
-            &stage);
+            &stage, VQHIP_PRECISION_FP32,
+            // the plain compress follows the handle's encode mode; a sidecar's records belong to the fp32 encode's indices
+            fr ? VQHIP_PRECISION_FP32 : c->encode_precision);
         if (rc) return rc;
         if (fr && !side.end_grid()) return fail(c, VQHIP_ERR_INVALID, "Failed to write to residual file.");
         st.leaves += G.n_leaves;

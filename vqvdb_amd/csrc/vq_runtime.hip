@@ -31,6 +31,7 @@
 #include "../../include/vqvdb_hip_bounded.h"
 #include "../../include/vqvdb_hip_residual.h"
 #include "../../include/vqvdb_hip_precision.h"
+#include "../../include/vqvdb_hip_encode_mode.h"
 #include "vq_buffers.h"
 #include "vq_switches.h"
 #include "vq_kernels.h"
@@ -46,6 +47,7 @@
 #include "vq_tail_rows.h"
 #include "vq_tail_groups.h"
 #include "vq_dec64_bf16.h"
+#include "vq_enc16_bf16.h"
 
 namespace {
 
@@ -157,6 +159,8 @@ const std::map<std::string, KernelInfo>& kernel_info()
         {"enc_conv_first", {2.0 * 221184, 264.0 * 2048}},   // conv_first_once_k: 264 16x16x4 MFMAs per leaf (kd skipped at the border planes, kh issued in full)
         {"enc_res16_conv1", {2.0 * 3538944, 2.0 * 3538944 * 0.7703}},
         {"enc_res16_conv2", {2.0 * 3538944, 2.0 * 3538944 * 0.7703}},
+        {"enc_res16_conv1_bf16", {2.0 * 3538944, 2.0 * 3538944 * 0.7703}},   // bf16 encode mode (vq_enc16_bf16.h): the same taps on the bf16 MFMA
+        {"enc_res16_conv2_bf16", {2.0 * 3538944, 2.0 * 3538944 * 0.7703}},
         {"enc_down", {2.0 * 2097152, 2.0 * 2097152 * 0.669922}},
         {"enc_res32_conv1", {2.0 * 1769472, 2.0 * 1769472 * 0.578704}},
         {"enc_res32_conv2", {2.0 * 1769472, 2.0 * 1769472 * 0.578704}},
@@ -266,6 +270,11 @@ struct vqhip_codec : Switches {   // the switch-controlled fields (n_cus, conv8_
     int decode_precision = VQHIP_PRECISION_FP32;
     DevBuf<uint16_t> bf_r64c1, bf_r64c2;
     bool bf_stale = true;
+    // bf16 encode mode (vqvdb_hip_encode_mode.h): the mode of the plain encode calls, the bf16 A fragments of the two 16 -> 16
+    // convs (grown at the first switch), and whether the fp32 fragments they are packed from have changed since (training)
+    int encode_precision = VQHIP_PRECISION_FP32;
+    DevBuf<uint16_t> bf_r16c1, bf_r16c2;
+    bool bf_enc_stale = true;
 };
 
 namespace {
@@ -1122,11 +1131,54 @@ bool use_split(const vqhip_codec* c, int nt, bool decode)
     return nt <= (decode ? 1728 : 1600);   // measured crossovers (r02 v8 kernels): encode 51 200 leaves, decode 55 296
 }
 
+// ---- bf16 encode mode (vqvdb_hip_encode_mode.h; kernels in vq_enc16_bf16.h) ----
+// The bf16 A fragments of the two 16 -> 16 convs, packed on the device from the live fp32 fragments ("r16c1.w", "r16c2.w": uploaded
+// at create, rebuilt by refrag_all after every training update, which marks these stale).  Buffers first, so that a failed
+// allocation leaves the handle as it was.  The pack is followed by a wait: it happens once per weight change, and a later call may
+// use another stream.
+int ensure_enc_bf16_frags(vqhip_codec* c, hipStream_t s)
+{
+    if (!c->bf_enc_stale && c->bf_r16c1 && c->bf_r16c2) return VQHIP_OK;
+    int rc;
+    if ((rc = ensure(c, c->bf_r16c1, (size_t)e16b::FRAG_ELEMS, "the bf16 fragments of encoder.pre.3.conv1"))) return rc;
+    if ((rc = ensure(c, c->bf_r16c2, (size_t)e16b::FRAG_ELEMS, "the bf16 fragments of encoder.pre.3.conv2"))) return rc;
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(e16b::conv_k<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e16b::LDS_BYTES));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(e16b::conv_k<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e16b::LDS_BYTES));
+    constexpr int wgs = (e16b::FRAG_ELEMS / 8 + 255) / 256;
+    hipLaunchKernelGGL(e16b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r16c1.w"], c->bf_r16c1.get());
+    hipLaunchKernelGGL(e16b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r16c2.w"], c->bf_r16c2.get());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(s));
+    c->bf_enc_stale = false;
+    return VQHIP_OK;
+}
+
+// e_a1 (+ its statistics) -> e_y4 (+ gn2's statistics) -> e_a6, for any number of tiles: ONE kernel per conv whatever the batch
+// size and launch sequence, so a leaf's bits do not depend on the launch path.  conv1 stores the sixteen half-row totals per leaf
+// and gn_combine_k<false> adds them in (oh, hw) order, as after conv8_lds_k.  The workgroups are persistent: grid from n_cus.
+void launch_enc16_bf16(vqhip_codec* c, Launcher& L, int nt, hipStream_t s)
+{
+    auto& a = c->act;
+    auto& w = c->dw;
+    EncStats S = enc_stats_of(c);
+    const int grid = std::min(4 * nt, c->n_cus);
+    e16b::Args B{};
+    B.in = a["e_a1"], B.out = a["e_y4"], B.wf = c->bf_r16c1, B.bias = w["r16c1.b"], B.n_groups = 4 * nt;
+    B.in_mean = S.a1m, B.in_rstd = S.a1r, B.in_gamma = w["r16g1.w"], B.in_beta = w["r16g1.b"];
+    B.part_s = reinterpret_cast<double*>(a["part_s"]), B.part_q = reinterpret_cast<double*>(a["part_q"]);
+    L.run("enc_res16_conv1_bf16", [&] { hipLaunchKernelGGL(e16b::conv_k<false>, dim3(grid), dim3(e16b::THREADS), e16b::LDS_BYTES, s, B); });
+    L.run("enc_stats_y4", [&] { hipLaunchKernelGGL((gn_combine_k<false>), dim3(nt), dim3(8 * 32), 0, s, B.part_s, B.part_q, S.y4m, S.y4r, 8, 1.0 / 1024.0); });
+    B.in = a["e_y4"], B.out = a["e_a6"], B.wf = c->bf_r16c2, B.bias = w["r16c2.b"], B.skip = a["e_a1"];
+    B.in_mean = S.y4m, B.in_rstd = S.y4r, B.in_gamma = w["r16g2.w"], B.in_beta = w["r16g2.b"];
+    B.part_s = nullptr, B.part_q = nullptr;
+    L.run("enc_res16_conv2_bf16", [&] { hipLaunchKernelGGL(e16b::conv_k<true>, dim3(grid), dim3(e16b::THREADS), e16b::LDS_BYTES, s, B); });
+}
+
 // Small batches (too few leaf tiles to fill 1024 SIMDs with one wave per tile): every layer is launched with its output
 // groups split over gridDim.y (and, for the tiniest batches, its output channels over gridDim.z) workgroups.  Each workgroup
 // covers whole statistics blocks (16 per leaf, the contract's 16-block rule) and stores their partial sums; gn_combine_k /
 // csum_combine_k add the blocks in order.  Same results bit for bit, 15-25x lower latency.
-int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, hipStream_t s, float* d_latent)
+int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, hipStream_t s, float* d_latent, int precision)
 {
     const int nt = (int)((n + 31) / 32);
     auto& a = c->act;
@@ -1176,7 +1228,9 @@ int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, h
         L.run("enc_gn_relu_a1", [&] { hipLaunchKernelGGL((gn_relu_stats_k<16, 512, 4>), dim3(g4, split_factor(g4, 8, 16, 1024)), dim3(256), 0, s, B); });
         combine("enc_stats_a1", 8, 1.0 / 1024.0, S.a1m, S.a1r);
     }
-    {
+    if (precision == VQHIP_PRECISION_BF16) {
+        launch_enc16_bf16(c, L, nt, s);
+    } else {
         ConvArgs A{};
         A.in = a["e_a1"], A.out = a["e_y4"], A.wfrag = w["r16c1.w"], A.bias_frag = w["r16c1.b"];
         A.in_mean = S.a1m, A.in_rstd = S.a1r, A.in_gamma = w["r16g1.w"], A.in_beta = w["r16g1.b"], A.n_tiles = nt;
@@ -1251,10 +1305,14 @@ int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, h
     return L.rc;
 }
 
-int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_idx, hipStream_t s, float* d_latent = nullptr)
+// precision: VQHIP_PRECISION_* of the two 16 -> 16 convs.  Only the plain encode entry points pass the handle's mode; the round
+// trip, every bounded, residual and size-sweep call, training and vqhip_multi_* take the default.
+int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_idx, hipStream_t s, float* d_latent = nullptr,
+                 int precision = VQHIP_PRECISION_FP32)
 {
     int rc = ensure_workspace(c, n);
     if (rc) return rc;
+    if (precision == VQHIP_PRECISION_BF16 && (rc = ensure_enc_bf16_frags(c, s))) return rc;
     const int nt = (int)((n + 31) / 32);
     auto& a = c->act;
     auto& w = c->dw;
@@ -1268,7 +1326,7 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
     const bool raw = c->first_raw && c->first_roll && !c->training && !c->full_training;
     c->cur_leaves = raw ? d_leaves : nullptr;
     if (!raw || xt) L.run("pack_leaves", [&] { hipLaunchKernelGGL(pack_leaves_k, dim3(nt, nt <= 128 ? 8 : 1), dim3(256), 0, s, d_leaves, a["xr"], xt, n); });
-    if (use_split(c, nt, false)) return encode_chunk_split(c, L, n, d_idx, s, d_latent);
+    if (use_split(c, nt, false)) return encode_chunk_split(c, L, n, d_idx, s, d_latent, precision);
     if (c->first_once && !c->first_raw && !c->training && !c->full_training) {
         // first conv once: conv + GroupNorm(4,16) + ReLU + statistics for res.gn1 out of the accumulators of a workgroup per 8-leaf group
         ConvArgs A{};
@@ -1299,7 +1357,8 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
             else hipLaunchKernelGGL(conv_first_k<1>, dim3(g4), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
         });
     }
-    {
+    if (precision == VQHIP_PRECISION_BF16) launch_enc16_bf16(c, L, nt, s);
+    else {
         ConvArgs A{};
         A.in = a["e_a1"], A.out = a["e_y4"], A.wfrag = w["r16c1.w"], A.bias_frag = w["r16c1.b"];
         A.in_mean = S.a1m, A.in_rstd = S.a1r, A.in_gamma = w["r16g1.w"], A.in_beta = w["r16g1.b"];
@@ -1316,7 +1375,7 @@ int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_id
             L.run("enc_stats_y4", [&] { hipLaunchKernelGGL((gn_combine_k<false, true>), dim3(nt), dim3(8 * 32), 0, s, A.part_s, A.part_q, S.y4m, S.y4r, 8, 1.0 / 1024.0); });
         }
     }
-    {
+    if (precision != VQHIP_PRECISION_BF16) {
         ConvArgs A{};
         A.in = a["e_y4"], A.out = a["e_a6"], A.wfrag = w["r16c2.w"], A.bias_frag = w["r16c2.b"], A.skip = a["e_a1"];
         A.in_mean = S.y4m, A.in_rstd = S.y4r, A.in_gamma = w["r16g2.w"], A.in_beta = w["r16g2.b"], A.n_tiles = nt;
@@ -1674,6 +1733,7 @@ int refresh_tables(vqhip_codec* c)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->tables_stale = false;
     c->bf_stale = true;   // every table that follows the live parameters is rebuilt after a training update, the bf16 decode mode's at its next call
+    c->bf_enc_stale = true;   // ... and the bf16 encode mode's (ensure_enc_bf16_frags)
     return VQHIP_OK;
 }
 
@@ -1706,7 +1766,7 @@ struct PipeStage {   // empty members are skipped
 };
 
 int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool want_stage, const ProduceFn& produce, const ConsumeFn& consume,
-                 const PipeStage* stage = nullptr, int decode_precision = VQHIP_PRECISION_FP32)
+                 const PipeStage* stage = nullptr, int decode_precision = VQHIP_PRECISION_FP32, int encode_precision = VQHIP_PRECISION_FP32)
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->chunk_fitted) fit_chunk_to_free_memory(c), c->chunk_fitted = true;
@@ -1726,7 +1786,7 @@ int run_pipeline(vqhip_codec* c, bool is_encode, int64_t n, int64_t step, bool w
     if (stage && stage->ensure && (rc = stage->ensure(step))) return rc;
     // what every chunk gets, in either arrangement below: its kernels on the compute stream ...
     auto chunk_work = [&](int64_t o, int64_t m, int slot) -> int {
-        int r = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream)
+        int r = is_encode ? encode_chunk(c, c->dev_leaves[slot], m, c->dev_idx[slot], c->stream, nullptr, encode_precision)
                           : decode_chunk(c, c->dev_idx[slot], m, c->dev_leaves[slot], c->stream, decode_precision);
         if (!r && stage && stage->device) r = stage->device(o, m, slot, c->stream);
         return r;
@@ -1824,7 +1884,7 @@ void scatter_leaves(float* const* dst, const float* src, int64_t m)
 
 // contiguous blocks or leaf-pointer arrays (vqhip_encode / _decode / _encode_leaves / _decode_leaves)
 int run_host_pipeline(vqhip_codec* c, bool is_encode, const void* in, void* out, int64_t n, const float* const* in_ptrs = nullptr,
-                      float* const* out_ptrs = nullptr, int decode_precision = VQHIP_PRECISION_FP32)
+                      float* const* out_ptrs = nullptr, int decode_precision = VQHIP_PRECISION_FP32, int encode_precision = VQHIP_PRECISION_FP32)
 {
     const size_t in_b = is_encode ? 2048 : 64, out_b = is_encode ? 64 : 2048;
     // leaf blocks go through pinned staging (copied by threads when large), not the runtime's pageable-copy path; a call that fits one
@@ -1844,7 +1904,7 @@ int run_host_pipeline(vqhip_codec* c, bool is_encode, const void* in, void* out,
             else host_parallel_copy(static_cast<char*>(out) + (size_t)ch.o * out_b, ch.result, (size_t)ch.m * out_b);
             return VQHIP_OK;
         },
-        nullptr, decode_precision);
+        nullptr, decode_precision, encode_precision);
 }
 
 }  // namespace
@@ -1994,7 +2054,7 @@ int vqhip_encode_device(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     for (int64_t o = 0; o < n; o += c->chunk) {
         const int64_t m = std::min(c->chunk, n - o);
-        int rc = encode_chunk(c, d_leaves + o * 512, m, d_idx + o * 64, s);
+        int rc = encode_chunk(c, d_leaves + o * 512, m, d_idx + o * 64, s, nullptr, c->encode_precision);
         if (rc) return rc;
     }
     return VQHIP_OK;
@@ -2020,7 +2080,7 @@ int vqhip_encode(vqhip_codec* c, const float* leaves, int64_t n, uint8_t* indice
 {
     if (!c) return VQHIP_ERR_INVALID;
     if (!leaves || !indices || n < 1) return fail(c, VQHIP_ERR_INVALID, "encode: null pointer or n_leaves < 1");
-    return run_host_pipeline(c, true, leaves, indices, n);
+    return run_host_pipeline(c, true, leaves, indices, n, nullptr, nullptr, VQHIP_PRECISION_FP32, c->encode_precision);
 }
 
 int vqhip_decode(vqhip_codec* c, const uint8_t* indices, int64_t n, float* leaves)
@@ -2034,7 +2094,7 @@ int vqhip_encode_leaves(vqhip_codec* c, const float* const* leaf_ptrs, int64_t n
 {
     if (!c) return VQHIP_ERR_INVALID;
     if (!leaf_ptrs || !indices || n < 1) return fail(c, VQHIP_ERR_INVALID, "encode_leaves: null pointer or n_leaves < 1");
-    return run_host_pipeline(c, true, nullptr, indices, n, leaf_ptrs, nullptr);
+    return run_host_pipeline(c, true, nullptr, indices, n, leaf_ptrs, nullptr, VQHIP_PRECISION_FP32, c->encode_precision);
 }
 
 int vqhip_decode_leaves(vqhip_codec* c, const uint8_t* indices, int64_t n, float* const* leaf_ptrs)
@@ -2408,6 +2468,27 @@ int vqhip_get_decode_mode(const vqhip_codec* c, int* mode)
 {
     if (!c || !mode) return VQHIP_ERR_INVALID;
     *mode = c->decode_precision;
+    return VQHIP_OK;
+}
+
+// include/vqvdb_hip_encode_mode.h
+int vqhip_set_encode_mode(vqhip_codec* c, int mode)
+{
+    if (!c) return VQHIP_ERR_INVALID;
+    if (mode != VQHIP_PRECISION_FP32 && mode != VQHIP_PRECISION_BF16)
+        return fail(c, VQHIP_ERR_INVALID, "set_encode_mode: mode " + std::to_string(mode) + " is neither VQHIP_PRECISION_FP32 (0) nor VQHIP_PRECISION_BF16 (1)");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mode == VQHIP_PRECISION_BF16)
+        if (int rc = ensure_enc_bf16_frags(c, c->stream)) return rc;   // (a failed allocation: VQHIP_ERR_NOMEM, the mode as it was)
+    c->encode_precision = mode;
+    return VQHIP_OK;
+}
+
+int vqhip_get_encode_mode(const vqhip_codec* c, int* mode)
+{
+    if (!c || !mode) return VQHIP_ERR_INVALID;
+    *mode = c->encode_precision;
     return VQHIP_OK;
 }
 

@@ -70,6 +70,7 @@ int refrag_all(vqhip_codec* c, hipStream_t s)
     int rc;
     float* d;
     c->bf_stale = true;   // the bf16 decode mode packs its fragments from "r64c1.w16" / "r64c2.w16" again at its next call (ensure_bf16_frags)
+    c->bf_enc_stale = true;   // ... and the bf16 encode mode its own from "r16c1.w" / "r16c2.w" (ensure_enc_bf16_frags)
     // The job list is built once (the tables are allocated on the first pass and never move, the parameters live in ft_P) and kept on the
     // device; every later call is ONE launch of refrag_multi_k.
     if (c->ft_refrag_jobs && c->ft_refrag_P != c->ft_P) {   // the cached table bakes in addresses inside the parameter block: rebuild if that moved
