@@ -153,6 +153,10 @@ ERR_FLOATS = 2   # VQHIP_ERR_FLOATS: per leaf max |x - x^|, sum (x - x^)^2
 VEC3_MASK_SYMBOLS = ["vqhip_vec3_mask_leaf_err_device", "vqhip_vec3_mask_residual_encode_device", "vqhip_vec3_mask_sweep_device",
                      "vqhip_vec3_mask_compress_residual", "vqhip_vec3_mask_sweep"]
 MASK_WORDS = 8   # VQHIP_VEC3_MASK_WORDS: uint64 words of one leaf's mask, bit L of word j = voxel 64 j + L
+# every symbol include/vqvdb_hip_vec3_active.h declares (records that hold only the active voxels; kept apart from the lists above)
+VEC3_ACTIVE_SYMBOLS = ["vqhip_vec3_active_record_bytes", "vqhip_vec3_active_encode_device", "vqhip_vec3_active_apply_device",
+                       "vqhip_vec3_active_sweep_device", "vqhip_vec3_active_compress", "vqhip_vec3_active_decompress",
+                       "vqhip_vec3_active_sweep"]
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
 
@@ -380,6 +384,16 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_mask_sweep.argtypes = [vp, vp, vp, i64, vp, ci, vp]
     for name in VEC3_MASK_SYMBOLS:
         getattr(lib, name).restype = ci
+    # include/vqvdb_hip_vec3_active.h
+    lib.vqhip_vec3_active_record_bytes.argtypes = [ci, ci]
+    lib.vqhip_vec3_active_encode_device.argtypes = [vp, vp, vp, vp, vp, i64, cf, vp, vp, vp, i64, vp]
+    lib.vqhip_vec3_active_apply_device.argtypes = [vp, vp, vp, i64, cf, vp, vp, vp, vp, vp]
+    lib.vqhip_vec3_active_sweep_device.argtypes = [vp, vp, vp, vp, vp, i64, vp, ci, vp, vp]
+    lib.vqhip_vec3_active_compress.argtypes = [vp, vp, vp, i64, cf, vp, vp, vp, vp, vp]
+    lib.vqhip_vec3_active_decompress.argtypes = [vp, vp, vp, i64, cf, vp, vp, i64, vp, vp]
+    lib.vqhip_vec3_active_sweep.argtypes = [vp, vp, vp, i64, vp, ci, vp]
+    for name in VEC3_ACTIVE_SYMBOLS:
+        getattr(lib, name).restype = i64 if name.endswith("_bytes") else ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -873,6 +887,113 @@ class HipVec3Codec:
         self._check(self._lib.vqhip_vec3_mask_sweep(self._h, leaves.ctypes.data, masks.ctypes.data, leaves.shape[0], tols.ctypes.data, len(tols),
                                                     hist.ctypes.data))
         return hist
+
+    # ---- records that hold only the active voxels: include/vqvdb_hip_vec3_active.h ----
+    @staticmethod
+    def check_background(background):
+        """None, or three real numbers -> float32 [3] (NaN, inf and -0 pass as they are)."""
+        if background is None:
+            return None
+        bg = np.ascontiguousarray(background, dtype=np.float32)
+        if bg.shape != (3,):
+            raise ValueError(f"background must be None or three numbers, got shape {list(bg.shape)}")
+        return bg
+
+    @staticmethod
+    def active_counts(masks) -> np.ndarray:
+        """int64 [n]: the active voxels of every leaf of masks uint64 [n,8]."""
+        return np.unpackbits(np.ascontiguousarray(masks).view(np.uint8).reshape(len(masks), 64), axis=1).sum(axis=1, dtype=np.int64)
+
+    @classmethod
+    def active_record_sizes(cls, leaf_code, masks) -> np.ndarray:
+        """int64 [n]: the bytes of every leaf's compact record: 0 kept, 8 ceil(3 A / 2) raw, 8 ceil(A / 64) (b0 + b1 + b2) quantised."""
+        c = np.asarray(leaf_code).astype(np.int64)
+        planes = cls.residual_record_sizes(leaf_code) // 64            # validates the codes; meaningless for the two sentinels
+        a = cls.active_counts(masks)
+        return np.where(c == VEC3_RES_KEPT, 0, np.where(c == VEC3_RES_RAW, 8 * ((3 * a + 1) // 2), 8 * ((a + 63) // 64) * planes))
+
+    def active_encode_device(self, leaves_ptr: int, recon_ptr: int, mask_ptr: int, leaf_err_ptr: int, n: int, tol: float, code_ptr: int,
+                             offsets_ptr: int, payload_ptr: int, payload_capacity: int, stream: int = 0):
+        """vqhip_vec3_active_encode_device: the codes of mask_residual_encode_device with records of the active voxels only."""
+        if n > 0 and not (leaves_ptr and recon_ptr and mask_ptr and leaf_err_ptr and code_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, mask, leaf_err, code and offsets are required")
+        if payload_capacity < 0:
+            raise ValueError("payload_capacity must be >= 0")
+        tol = self.check_tol(tol)
+        self._check(self._lib.vqhip_vec3_active_encode_device(self._h, leaves_ptr, recon_ptr, mask_ptr, leaf_err_ptr, n, tol, code_ptr, offsets_ptr,
+                                                              payload_ptr or None, payload_capacity, stream or None))
+
+    def active_apply_device(self, leaves_ptr: int, mask_ptr: int, n: int, tol: float, code_ptr: int, offsets_ptr: int, payload_ptr: int,
+                            background=None, stream: int = 0):
+        """vqhip_vec3_active_apply_device: the decoded leaves at leaves_ptr corrected in place at their active voxels; with a
+        ``background`` of three numbers every inactive voxel receives it, with None inactive voxels are not touched.  The device
+        arrays are trusted."""
+        if n > 0 and not (leaves_ptr and mask_ptr and code_ptr and offsets_ptr):
+            raise ValueError("NULL device pointer: leaves, mask, code and offsets are required")
+        tol = self.check_tol(tol)
+        bg = self.check_background(background)
+        self._check(self._lib.vqhip_vec3_active_apply_device(self._h, leaves_ptr, mask_ptr, n, tol, code_ptr, offsets_ptr, payload_ptr or None,
+                                                             None if bg is None else bg.ctypes.data, stream or None))
+
+    def active_sweep_device(self, leaves_ptr: int, recon_ptr: int, mask_ptr: int, leaf_err_ptr: int, n: int, tols, bytes_ptr: int, stream: int = 0):
+        """vqhip_vec3_active_sweep_device: ADDS the compact payload bytes of n leaves at every rung to bytes_ptr, a device buffer of
+        len(tols) int64 that the caller zeroes before the first call."""
+        tols = self.check_tols(tols)
+        if n > 0 and not (leaves_ptr and recon_ptr and mask_ptr and leaf_err_ptr and bytes_ptr):
+            raise ValueError("NULL device pointer: leaves, recon, mask, leaf_err and bytes are required")
+        self._check(self._lib.vqhip_vec3_active_sweep_device(self._h, leaves_ptr, recon_ptr, mask_ptr, leaf_err_ptr, n, tols.ctypes.data, len(tols),
+                                                             bytes_ptr, stream or None))
+
+    def compress_active(self, leaves: np.ndarray, masks: np.ndarray, tol: float, return_leaf_err: bool = False):
+        """compress_residual_masked with records that hold only the active voxels: the same indices and codes, a payload that
+        shrinks with every leaf's active count.  -> (indices, leaf_code, payload[, masked leaf_err]), read by decompress_active
+        with the same masks."""
+        leaves = self.check_leaves(leaves)
+        n = leaves.shape[0]
+        masks = check_masks(masks, n)
+        tol = self.check_tol(tol)
+        idx, err = np.empty((n, 64), dtype=np.uint16), np.empty((n, VEC3_ERR_FLOATS), dtype=np.float32)
+        lc, payload, nbytes = np.empty(n, dtype=np.uint16), np.empty(n * 6144, dtype=np.uint8), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_active_compress(self._h, leaves.ctypes.data, masks.ctypes.data, n, tol, idx.ctypes.data, err.ctypes.data,
+                                                         lc.ctypes.data, payload.ctypes.data, ctypes.byref(nbytes)))
+        out = (idx, lc, payload[:nbytes.value].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def decompress_active(self, indices: np.ndarray, masks: np.ndarray, tol: float, leaf_code, payload, background=None) -> np.ndarray:
+        """Decoded leaves [n,512,3] with the records of compress_active (same masks, same ``tol``, same precision mode) applied at
+        the active voxels; inactive voxels hold ``background`` (three numbers) or, with None, what the decoder gave."""
+        indices = self.check_indices(indices)
+        n = indices.shape[0]
+        masks = check_masks(masks, n)
+        tol = self.check_tol(tol)
+        bg = self.check_background(background)
+        if not isinstance(leaf_code, np.ndarray) or leaf_code.dtype != np.uint16:
+            raise TypeError("leaf_code must be a uint16 numpy array")
+        lc = np.ascontiguousarray(leaf_code).reshape(-1)
+        if len(lc) != n:
+            raise ValueError(f"{n} leaves but {len(lc)} codes")
+        if isinstance(payload, (bytes, bytearray, memoryview)):
+            payload = np.frombuffer(payload, dtype=np.uint8)
+        if not isinstance(payload, np.ndarray) or payload.dtype != np.uint8:
+            raise TypeError("payload must be bytes or a uint8 numpy array")
+        pl = np.ascontiguousarray(payload).reshape(-1)
+        need = int(self.active_record_sizes(lc, masks).sum())
+        if need != len(pl):
+            raise ValueError(f"the codes and masks need {need} payload bytes, got {len(pl)}")
+        out = np.empty((n, 512, 3), dtype=np.float32)
+        self._check(self._lib.vqhip_vec3_active_decompress(self._h, indices.ctypes.data, masks.ctypes.data, n, tol, lc.ctypes.data, pl.ctypes.data,
+                                                           len(pl), None if bg is None else bg.ctypes.data, out.ctypes.data))
+        return out
+
+    def rate_sweep_active(self, leaves: np.ndarray, masks: np.ndarray, tols) -> np.ndarray:
+        """-> int64 [T]: the payload bytes of compress_active at every rung of ``tols``."""
+        leaves = self.check_leaves(leaves)
+        masks = check_masks(masks, leaves.shape[0])
+        tols = self.check_tols(tols)
+        out = np.empty(len(tols), dtype=np.int64)
+        self._check(self._lib.vqhip_vec3_active_sweep(self._h, leaves.ctypes.data, masks.ctypes.data, leaves.shape[0], tols.ctypes.data, len(tols),
+                                                      out.ctypes.data))
+        return out
 
     # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----
     @staticmethod
@@ -1664,6 +1785,21 @@ def vec3_rate_pick(hist, tols, payload_budget: int) -> int:
     if best < 0:
         raise ValueError(f"no rung fits {payload_budget} bytes")
     return best
+
+
+def vec3_active_record_bytes(code: int, active: int) -> int:
+    """vqhip_vec3_active_record_bytes: the bytes of the compact record of ``code`` on a leaf with ``active`` active voxels
+    (0 kept, 8 ceil(3 A / 2) raw, 8 ceil(A / 64) (b0 + b1 + b2) quantised).  Raises ValueError for a code that is neither a
+    sentinel nor three widths of 0..16 or an ``active`` outside 0..512."""
+    for v, what in ((code, "code"), (active, "active")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{what} must be an integer, got {v!r}")
+    if not -2**31 <= code < 2**31 or not -2**31 <= active < 2**31:
+        raise ValueError(f"code {code} or active {active} is out of range")
+    size = int(load_library().vqhip_vec3_active_record_bytes(int(code), int(active)))
+    if size < 0:
+        raise ValueError(f"code 0x{int(code) & 0xFFFFFFFF:X} with {active} active voxels has no record size")
+    return size
 
 
 class HipMultiCodec:

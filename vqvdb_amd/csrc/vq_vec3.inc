@@ -44,6 +44,8 @@ struct vqhip_vec3_codec {
     DevBuf<int64_t> rate_hist;
     // active-voxel masks (vq_vec3_mask.inc), host calls: one chunk's masks [m][8]
     DevBuf<uint64_t> mk_mask;
+    // compact records (vq_vec3_active.inc), host sweep: the payload bytes of every rung [64]
+    DevBuf<int64_t> ac_bytes;
     struct Dbg {
         DevBuf<float> p;
         int64_t n = 0;
