@@ -1,7 +1,7 @@
 """The two generic conv kernels at the batch sizes where the launch code changes configuration (vq_kernels.h: RowsCfg / Mfma32Cfg;
 vq_runtime.hip: launch_rows / launch_mfma32 derive block, grid and dynamic LDS from the configuration).
 
-The sizes come from the selection conditions in encode_chunk_split / decode_chunk_split (gh = ceil(2 nt / 8) workgroups of 8 half tiles,
+The sizes come from the selection conditions of the split path in enc_down / enc_res32 / dec_res64 (gh = ceil(2 nt / 8) workgroups of 8 half tiles,
 psr = 16 ranges of output rows at these sizes):
   encode  1024 leaves: gh psr 2 = 256, the last size of the cout-split x2 kernels     1056: 288, the position-split kernels
   decode  2048 leaves: gh psr 4 = 1024, the last size of the x4 kernels (LDS-resident quarters, or streamed with VQHIP_R64S=stream)

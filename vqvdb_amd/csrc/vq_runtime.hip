@@ -193,7 +193,6 @@ struct vqhip_codec : Switches {   // the switch-controlled fields (n_cus, conv8_
     hipStream_t stream = nullptr;
     int64_t chunk = 65536;
     int n_cus_device = 256;  // compute units of the device itself (CU mask of the reduction stream)
-    const float* cur_leaves = nullptr;   // the current pass's input leaves (device), for the split path's first conv
     int split_tiles = -1;    // position-split path: -1 = automatic (measured crossovers, use_split), >= 0 = plain tile threshold
 
     // device weights
@@ -239,14 +238,13 @@ struct vqhip_codec : Switches {   // the switch-controlled fields (n_cus, conv8_
     DevBuf<char> ft_ws;                                            // training workspace (saved activations, gradients)
     int64_t ft_tiles = 0;                                          // ... laid out for this many tiles
     DevBuf<char> ft_part;                                          // partial-gradient scratch
-    bool full_training = false, keep_y1 = false, weights_stale = false;
+    bool full_training = false, weights_stale = false;
     hipStream_t ft_side = nullptr;
     hipStream_t ft_red_shared = nullptr;   // ... the same on a plain stream (shares a hardware queue with the weight-gradient stream): large batches
     bool ft_egate_early = false;           // this step's encoder attention gates were computed beside the forward pass
     hipStream_t ft_red = nullptr;    // third stream of the training step (round 6): the small reductions nothing on the data-gradient chain waits for (bias sums, GroupNorm-affine and attention-weight reductions)
     std::vector<hipEvent_t> ft_ev;   // fork / join events of the side stream, reused every step
     size_t ft_ev_next = 0;
-    float* z4_out = nullptr;   // set around encode_chunk by the training forward: latent also in the L4 layout
     DevBuf<char> tr_part;      // per-(code, row segment) partial statistics
     DevBuf<float> tr_recon;    // reconstruction scratch of vqhip_train_eval_device
     DevBuf<double> tr_loss_part;
@@ -860,7 +858,7 @@ const ActSpec kActs[] = {
 };
 constexpr int kRegions = 3;
 
-bool want_full_layout(const vqhip_codec* c) { return c->debug || c->training || c->full_training || c->keep_y1; }
+bool want_full_layout(const vqhip_codec* c) { return c->debug || c->training || c->full_training; }
 
 size_t workspace_bytes(int64_t tiles, bool full)
 {
@@ -1073,6 +1071,19 @@ int init_kernel_attrs(vqhip_codec* c)
     if ((rc = set_lds(c, latent_assign_k<4>, LDS_LATENT))) return rc;
     return VQHIP_OK;
 }
+// The order of the other inference templates, as the list above keeps that of its kernels: a template is instantiated, and so placed
+// in the code object, at its first mention in this file, and tools/kernel_isa_diff.py pairs the kernels of two builds by position.
+// The layer stages below name them in the order of the layers, which is not the order they have in the code object.
+[[maybe_unused]] const void* const kInstantiationOrder[] = {
+    (const void*)e16b::conv_k<false>, (const void*)e16b::conv_k<true>, (const void*)gn_combine_k<false>, (const void*)conv_first_k<0, 0, true>,
+    (const void*)conv_first_k<0>, (const void*)conv_first_roll_k<1, true>, (const void*)conv_first_roll_k<1>, (const void*)conv_first_k<1>,
+    (const void*)conv_first_k<2, 0, true>, (const void*)conv_first_k<2>, (const void*)gn_relu_stats_k<16, 512, 4>, (const void*)conv8_c16_k<2, false, true>,
+    (const void*)conv8_c16_k<4, false, true>, (const void*)gn_combine_k<false, true>, (const void*)conv8_c16_k<2, true, false>,
+    (const void*)conv8_c16_k<4, true, false>, (const void*)csum_combine_k<32>, (const void*)vq_folded_k<8>, (const void*)vq_folded_k<2>,
+    (const void*)conv_first_roll_k<0, true>, (const void*)conv_first_roll_k<0>, (const void*)d64b::conv_k<false>, (const void*)d64b::conv_k<true>,
+    (const void*)gn_combine_k<true>, (const void*)csum_combine_k<64>, (const void*)stem_fused_k<16>, (const void*)stem_fused_k<8>,
+    (const void*)gn_relu_stats_k<64, 64, 8>,
+};
 
 // Where the encoder's GroupNorm statistics and channel sums live.  Inference ping-pongs two buffers (st_a / st_b); the full training
 // step needs every layer's statistics again in its backward pass, so there each tensor's statistics go to their own buffer of the
@@ -1081,34 +1092,14 @@ int init_kernel_attrs(vqhip_codec* c)
 struct EncStats {
     float *y1m, *y1r, *a1m, *a1r, *y4m, *y4r, *x7m, *x7r, *y9m, *y9r, *csum;
 };
-EncStats enc_stats_of(vqhip_codec* c)
+EncStats enc_stats_of(vqhip_codec* c, bool train_forward)
 {
     auto& a = c->act;
-    if (c->full_training && c->keep_y1)
+    if (train_forward)
         return {a["ts_gn0.mean"], a["ts_gn0.rstd"], a["ts_r16g1.mean"], a["ts_r16g1.rstd"], a["ts_r16g2.mean"], a["ts_r16g2.rstd"],
                 a["ts_r32g1.mean"], a["ts_r32g1.rstd"], a["ts_r32g2.mean"], a["ts_r32g2.rstd"], a["ts_ecsum"]};
     return {a["st_a.mean"], a["st_a.rstd"], a["st_b.mean"], a["st_b.rstd"], a["st_a.mean"], a["st_a.rstd"],
             a["st_b.mean"], a["st_b.rstd"], a["st_a.mean"], a["st_a.rstd"], a["csum"]};
-}
-
-void launch_latent_assign(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, float* d_latent, hipStream_t s, int split)
-{
-    auto& a = c->act;
-    auto& w = c->dw;
-    const int nt = (int)((n + 31) / 32);
-    // training forward: latent materialised, reference-faithful distance against the live codebook
-    L.run("train_codebook_frag", [&] { hipLaunchKernelGGL(codebook_frag_k, dim3(33), dim3(256), 0, s, w["cb"], w["tr.efrag"], w["tr.ee"]); });
-    LatentArgs A{};
-    A.in = a["e_x11"], A.se_csum = enc_stats_of(c).csum, A.se_fc0 = w["efc0"], A.se_fc2 = w["efc2"];
-    A.wproj = w["tr.wproj"], A.bproj = w["tr.bproj"], A.efrag = w["tr.efrag"], A.ee_frag = w["tr.ee"];
-    A.idx = d_idx, A.z = d_latent, A.z4 = c->z4_out, A.n_leaves = n, A.n_tiles = nt;
-    if (split <= 1 && nt >= 1024) L.run("train_latent_assign", [&] { hipLaunchKernelGGL(latent_assign_k<8>, dim3((nt + 7) / 8), dim3(512), LDS_LATENT, s, A); });
-    else if (split > 1 && nt >= 8) {
-        // small training batches: 144 KB of LDS = one workgroup per CU, so FOUR waves per workgroup (every SIMD busy; two left half of
-        // the CU idle) and twice the position ranges: 0.236 -> 0.13 ms at 2048 leaves
-        const int sp = std::min(64, 2 * split);
-        L.run("train_latent_assign", [&] { hipLaunchKernelGGL(latent_assign_k<4>, dim3((nt + 3) / 4, sp), dim3(256), LDS_LATENT, s, A); });
-    } else L.run("train_latent_assign", [&] { hipLaunchKernelGGL(latent_assign_k<2>, dim3((nt + 1) / 2, split > 1 ? split : 1), dim3(128), LDS_LATENT, s, A); });
 }
 
 // gridDim.y for a position-split launch of `wgs` workgroups: enough ranges to reach `target` workgroups (about two rounds
@@ -1131,437 +1122,500 @@ bool use_split(const vqhip_codec* c, int nt, bool decode)
     return nt <= (decode ? 1728 : 1600);   // measured crossovers (r02 v8 kernels): encode 51 200 leaves, decode 55 296
 }
 
-// ---- bf16 encode mode (vqvdb_hip_encode_mode.h; kernels in vq_enc16_bf16.h) ----
-// The bf16 A fragments of the two 16 -> 16 convs, packed on the device from the live fp32 fragments ("r16c1.w", "r16c2.w": uploaded
-// at create, rebuilt by refrag_all after every training update, which marks these stale).  Buffers first, so that a failed
-// allocation leaves the handle as it was.  The pack is followed by a wait: it happens once per weight change, and a later call may
-// use another stream.
-int ensure_enc_bf16_frags(vqhip_codec* c, hipStream_t s)
+// One encode or decode pass of n leaves on stream s: what the layer stages below take.  A stage states its layer's tensors, weights,
+// GroupNorm inputs and step table once; the path decides the kernel, the launch geometry and the route of the output statistics.
+//   split false: one wave (or workgroup) per tile, and the kernel finishes its statistics itself (out_mean / out_rstd / out_csum).
+//   split true: small batches (too few leaf tiles to fill 1024 SIMDs with one wave per tile).  Every layer is launched with its
+//     output groups split over gridDim.y (and, for the tiniest batches, its output channels over gridDim.z) workgroups.  Each
+//     workgroup covers whole statistics blocks (16 per leaf, the contract's 16-block rule) and stores their partial sums (part_s /
+//     part_q / part_c, found through grp_start); gn_combine_k / csum_combine_k add the blocks in order.  Same results bit for bit,
+//     15-25x lower latency.  The names of these launches end in _s.
+struct Pass {
+    vqhip_codec* c;
+    hipStream_t s;
+    Launcher L;
+    int64_t n;
+    int nt;             // 32-leaf tiles
+    const bool split;   // use_split
+    int precision;      // VQHIP_PRECISION_* of the two 16 -> 16 convs (encode) / 64 -> 64 convs (decode)
+};
+struct EncPass : Pass {
+    EncStats S;
+    const float* d_leaves;
+    bool raw;           // the first conv reads d_leaves itself, not the row layout xr
+    uint8_t* d_idx;
+    float* d_latent;    // training: the latent rows are stored and assigned against the live codebook
+    float* latent_l4;   // the forward of the full training step: the latent in the L4 layout as well ...
+    bool keep_y1;       // ... the first conv's raw output kept, and every layer's statistics in a buffer of their own (EncStats)
+};
+struct DecPass : Pass {
+    const uint8_t* d_idx;
+    float* d_out;
+};
+
+double* part_s(vqhip_codec* c) { return reinterpret_cast<double*>(c->act["part_s"]); }
+double* part_q(vqhip_codec* c) { return reinterpret_cast<double*>(c->act["part_q"]); }
+// the first step of each output group in a step table, by the table's name + ".grp" (a literal: no string is built per launch)
+const int* grp(vqhip_codec* c, const char* name) { return reinterpret_cast<const int*>(c->dw[name]); }
+
+// The combine kernels behind a launch that stored per-block partials.  GroupNorm statistics of `groups` groups from part_s / part_q:
+void combine(Pass& P, const char* name, int groups, double inv_n, float* mean, float* rstd)
 {
-    if (!c->bf_enc_stale && c->bf_r16c1 && c->bf_r16c2) return VQHIP_OK;
-    int rc;
-    if ((rc = ensure(c, c->bf_r16c1, (size_t)e16b::FRAG_ELEMS, "the bf16 fragments of encoder.pre.3.conv1"))) return rc;
-    if ((rc = ensure(c, c->bf_r16c2, (size_t)e16b::FRAG_ELEMS, "the bf16 fragments of encoder.pre.3.conv2"))) return rc;
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(e16b::conv_k<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e16b::LDS_BYTES));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(e16b::conv_k<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e16b::LDS_BYTES));
-    constexpr int wgs = (e16b::FRAG_ELEMS / 8 + 255) / 256;
-    hipLaunchKernelGGL(e16b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r16c1.w"], c->bf_r16c1.get());
-    hipLaunchKernelGGL(e16b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r16c2.w"], c->bf_r16c2.get());
+    P.L.run(name, [&] { hipLaunchKernelGGL(gn_combine_k<false>, dim3(P.nt), dim3(groups * 32), 0, P.s, part_s(P.c), part_q(P.c), mean, rstd, groups, inv_n); });
+}
+// ... of GroupNorm(8,16) from one partial per output half row (ps, pq), added row-major
+void combine_rows(Pass& P, const char* name, const double* ps, const double* pq, float* mean, float* rstd)
+{
+    P.L.run(name, [&] { hipLaunchKernelGGL((gn_combine_k<false, true>), dim3(P.nt), dim3(8 * 32), 0, P.s, ps, pq, mean, rstd, 8, 1.0 / 1024.0); });
+}
+// ... of GroupNorm(8,64): 16 slots = the 4-channel halves of a group
+void combine_pairs(Pass& P, const char* name, float* mean, float* rstd)
+{
+    P.L.run(name, [&] { hipLaunchKernelGGL(gn_combine_k<true>, dim3(P.nt), dim3(512), 0, P.s, part_s(P.c), part_q(P.c), mean, rstd, 8, 1.0 / 512.0); });
+}
+// ... and the channel sums of C channels from part_c, with the attention gates (computed once per tile here, read by the next stage)
+template <int C>
+void combine_csum(Pass& P, const char* name, float* csum, const float* fc0, const float* fc2)
+{
+    auto& a = P.c->act;
+    P.L.run(name, [&] { hipLaunchKernelGGL((csum_combine_k<C>), dim3(P.nt), dim3(64 * C / 8), 0, P.s, a["part_c"], csum, fc0, fc2, a["gate"]); });
+}
+
+// ---- bf16 modes (vqvdb_hip_encode_mode.h, DESIGN 24, kernels in vq_enc16_bf16.h; vqvdb_hip_precision.h, DESIGN 23, vq_dec64_bf16.h) ----
+// The bf16 A fragments of a mode's two convs, packed on the device from the live fp32 fragments `src` (uploaded at create, rebuilt by
+// refrag_all after every training update, which marks the mode's fragments stale).  Buffers first, so that a failed allocation
+// leaves the handle as it was.  The pack is followed by a wait: it happens once per weight change, and a later call may use
+// another stream.
+struct Bf16Conv {
+    DevBuf<uint16_t>& frag;
+    const char* src;
+    const void* kernel;
+    const char* what;
+};
+int ensure_bf16_frags(vqhip_codec* c, hipStream_t s, bool& stale, Bf16Conv (&&convs)[2], size_t frag_elems, void (*pack)(const float*, uint16_t*), size_t lds)
+{
+    if (!stale && convs[0].frag && convs[1].frag) return VQHIP_OK;
+    for (Bf16Conv& v : convs)
+        if (int rc = ensure(c, v.frag, frag_elems, v.what)) return rc;
+    for (Bf16Conv& v : convs) HIPCHK(c, hipFuncSetAttribute(v.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (Bf16Conv& v : convs) hipLaunchKernelGGL(pack, dim3((frag_elems / 8 + 255) / 256), dim3(256), 0, s, c->dw[v.src], v.frag.get());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(s));
-    c->bf_enc_stale = false;
+    stale = false;
     return VQHIP_OK;
 }
-
-// e_a1 (+ its statistics) -> e_y4 (+ gn2's statistics) -> e_a6, for any number of tiles: ONE kernel per conv whatever the batch
-// size and launch sequence, so a leaf's bits do not depend on the launch path.  conv1 stores the sixteen half-row totals per leaf
-// and gn_combine_k<false> adds them in (oh, hw) order, as after conv8_lds_k.  The workgroups are persistent: grid from n_cus.
-void launch_enc16_bf16(vqhip_codec* c, Launcher& L, int nt, hipStream_t s)
+int ensure_enc_bf16_frags(vqhip_codec* c, hipStream_t s)
 {
-    auto& a = c->act;
-    auto& w = c->dw;
-    EncStats S = enc_stats_of(c);
-    const int grid = std::min(4 * nt, c->n_cus);
-    e16b::Args B{};
-    B.in = a["e_a1"], B.out = a["e_y4"], B.wf = c->bf_r16c1, B.bias = w["r16c1.b"], B.n_groups = 4 * nt;
-    B.in_mean = S.a1m, B.in_rstd = S.a1r, B.in_gamma = w["r16g1.w"], B.in_beta = w["r16g1.b"];
-    B.part_s = reinterpret_cast<double*>(a["part_s"]), B.part_q = reinterpret_cast<double*>(a["part_q"]);
-    L.run("enc_res16_conv1_bf16", [&] { hipLaunchKernelGGL(e16b::conv_k<false>, dim3(grid), dim3(e16b::THREADS), e16b::LDS_BYTES, s, B); });
-    L.run("enc_stats_y4", [&] { hipLaunchKernelGGL((gn_combine_k<false>), dim3(nt), dim3(8 * 32), 0, s, B.part_s, B.part_q, S.y4m, S.y4r, 8, 1.0 / 1024.0); });
-    B.in = a["e_y4"], B.out = a["e_a6"], B.wf = c->bf_r16c2, B.bias = w["r16c2.b"], B.skip = a["e_a1"];
-    B.in_mean = S.y4m, B.in_rstd = S.y4r, B.in_gamma = w["r16g2.w"], B.in_beta = w["r16g2.b"];
-    B.part_s = nullptr, B.part_q = nullptr;
-    L.run("enc_res16_conv2_bf16", [&] { hipLaunchKernelGGL(e16b::conv_k<true>, dim3(grid), dim3(e16b::THREADS), e16b::LDS_BYTES, s, B); });
+    return ensure_bf16_frags(c, s, c->bf_enc_stale,
+                             {{c->bf_r16c1, "r16c1.w", reinterpret_cast<const void*>(e16b::conv_k<false>), "the bf16 fragments of encoder.pre.3.conv1"},
+                              {c->bf_r16c2, "r16c2.w", reinterpret_cast<const void*>(e16b::conv_k<true>), "the bf16 fragments of encoder.pre.3.conv2"}},
+                             e16b::FRAG_ELEMS, e16b::frag_k, e16b::LDS_BYTES);
+}
+int ensure_dec_bf16_frags(vqhip_codec* c, hipStream_t s)
+{
+    return ensure_bf16_frags(c, s, c->bf_stale,
+                             {{c->bf_r64c1, "r64c1.w16", reinterpret_cast<const void*>(d64b::conv_k<false>), "the bf16 fragments of decoder.res_stack.0.conv1"},
+                              {c->bf_r64c2, "r64c2.w16", reinterpret_cast<const void*>(d64b::conv_k<true>), "the bf16 fragments of decoder.res_stack.0.conv2"}},
+                             d64b::FRAG_ELEMS, d64b::frag_k, d64b::LDS_BYTES);
 }
 
-// Small batches (too few leaf tiles to fill 1024 SIMDs with one wave per tile): every layer is launched with its output
-// groups split over gridDim.y (and, for the tiniest batches, its output channels over gridDim.z) workgroups.  Each workgroup
-// covers whole statistics blocks (16 per leaf, the contract's 16-block rule) and stores their partial sums; gn_combine_k /
-// csum_combine_k add the blocks in order.  Same results bit for bit, 15-25x lower latency.
-int encode_chunk_split(vqhip_codec* c, Launcher& L, int64_t n, uint8_t* d_idx, hipStream_t s, float* d_latent, int precision)
+// ---- the encoder's stages: xr -> a1 -> y4 -> a6 (skip a1) -> x7 -> y9 -> x11 (skip x7) -> indices ----
+// first conv + GroupNorm(4,16) + ReLU: xr (or the caller's leaves) -> e_a1, with the statistics of y1 and those of a1 for res.gn1
+void enc_first(EncPass& P)
 {
-    const int nt = (int)((n + 31) / 32);
-    auto& a = c->act;
-    auto& w = c->dw;
-    EncStats S = enc_stats_of(c);
-    auto od = [&](const char* name) { return reinterpret_cast<const int*>(w[std::string(name) + ".grp"]); };
-    const int g4 = (nt + 3) / 4, g2 = (nt + 1) / 2, gh = (2 * nt + 7) / 8;   // gh: workgroups of 8 half tiles (conv_rows16_k)
-    double* ps = reinterpret_cast<double*>(a["part_s"]);
-    double* pq = reinterpret_cast<double*>(a["part_q"]);
-    // Every launch covers whole statistics blocks (16 per leaf) and stores their sums; gn_combine_k adds them in block order.
-    auto combine = [&](const char* name, int groups, double inv_n, float* mean, float* rstd) {
-        L.run(name, [&] { hipLaunchKernelGGL(gn_combine_k<false>, dim3(nt), dim3(groups * 32), 0, s, ps, pq, mean, rstd, groups, inv_n); });
-    };
-    if (nt >= 256) {
-        // mid-size batches: the first conv twice (statistics, then recompute + normalise + store), like the one-wave-per-tile path,
-        // instead of storing its raw output and normalising it in an elementwise pass (2 x 32 KiB per leaf less traffic)
-        ConvArgs A{};
-        const bool raw = c->cur_leaves != nullptr;
-        A.in = raw ? c->cur_leaves : a["xr"], A.out = (c->debug || c->keep_y1) ? a["e_y1"] : nullptr, A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"], A.n_tiles = nt, A.n_leaves = n;
-        A.n_steps = c->nsteps["steps.rows8kd"], A.grp_start = od("steps.rows8kd"), A.part_s = ps, A.part_q = pq;
-        const int psf = split_factor(g4, 8, 16, 1024);
-        L.run("enc_conv_first_stats_s", [&] {
-            if (raw) hipLaunchKernelGGL((conv_first_k<0, 0, true>), dim3(g4, psf), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-            else hipLaunchKernelGGL(conv_first_k<0>, dim3(g4, psf), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt, g4 = (nt + 3) / 4, gq = (2 * nt + 3) / 4, psf = P.split ? split_factor(g4, 8, 16, 1024) : 1;
+    const int4* steps = (const int4*)w["steps.rows8kd"];
+    float* y1 = (c->debug || P.keep_y1) ? a["e_y1"] : nullptr;
+    ConvArgs A{};
+    A.in = P.raw ? P.d_leaves : a["xr"], A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"], A.n_tiles = nt, A.n_leaves = P.n;
+    A.n_steps = c->nsteps["steps.rows8kd"];
+    if (P.split) A.grp_start = grp(c, "steps.rows8kd.grp"), A.part_s = part_s(c), A.part_q = part_q(c);
+    if (!P.split && c->first_once && !c->first_raw && !c->training && !c->full_training) {
+        // first conv once: conv + GroupNorm(4,16) + ReLU + statistics for res.gn1 out of the accumulators of a workgroup per 8-leaf group
+        A.out = a["e_a1"], A.in_gamma = w["eg0.w"], A.in_beta = w["eg0.b"], A.out_mean = P.S.a1m, A.out_rstd = P.S.a1r;
+        P.L.run("enc_conv_first", [&] { hipLaunchKernelGGL(conv_first_once_k, dim3(std::min(4 * nt, c->n_cus)), dim3(512), 0, P.s, A, y1, P.S.y1m, P.S.y1r); });
+        return;
+    }
+    if (P.split && nt < 256) {   // small batches: the raw output stored, normalised in an elementwise pass
+        A.out = a["e_y1"];
+        P.L.run("enc_conv_first_s", [&] {
+            if (P.raw) hipLaunchKernelGGL((conv_first_k<2, 0, true>), dim3(g4, psf), dim3(256), 0, P.s, A, steps);
+            else hipLaunchKernelGGL(conv_first_k<2>, dim3(g4, psf), dim3(256), 0, P.s, A, steps);
         });
-        combine("enc_stats_y1", 4, 1.0 / 2048.0, S.y1m, S.y1r);
-        A.out = a["e_a1"], A.in_mean = S.y1m, A.in_rstd = S.y1r, A.in_gamma = w["eg0.w"], A.in_beta = w["eg0.b"];
-        L.run("enc_conv_first_gn_s", [&] {   // (rolling row window: vq_first_roll.h)
-            if (raw) hipLaunchKernelGGL((conv_first_roll_k<1, true>), dim3((2 * nt + 3) / 4, psf), dim3(256), 0, s, A);
-            else if (c->first_roll) hipLaunchKernelGGL(conv_first_roll_k<1>, dim3((2 * nt + 3) / 4, psf), dim3(256), 0, s, A);
-            else hipLaunchKernelGGL(conv_first_k<1>, dim3(g4, psf), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-        });
-        combine("enc_stats_a1", 8, 1.0 / 1024.0, S.a1m, S.a1r);
-    } else {
-        ConvArgs A{};
-        const bool raw = c->cur_leaves != nullptr;
-        A.in = raw ? c->cur_leaves : a["xr"], A.out = a["e_y1"], A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"], A.n_tiles = nt, A.n_leaves = n;
-        A.n_steps = c->nsteps["steps.rows8kd"], A.grp_start = od("steps.rows8kd"), A.part_s = ps, A.part_q = pq;
-        L.run("enc_conv_first_s", [&] {
-            if (raw) hipLaunchKernelGGL((conv_first_k<2, 0, true>), dim3(g4, split_factor(g4, 8, 16, 1024)), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-            else hipLaunchKernelGGL(conv_first_k<2>, dim3(g4, split_factor(g4, 8, 16, 1024)), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-        });
-        combine("enc_stats_y1", 4, 1.0 / 2048.0, S.y1m, S.y1r);
+        combine(P, "enc_stats_y1", 4, 1.0 / 2048.0, P.S.y1m, P.S.y1r);
         ConvArgs B{};
-        B.in = a["e_y1"], B.out = a["e_a1"], B.in_mean = S.y1m, B.in_rstd = S.y1r, B.in_gamma = w["eg0.w"], B.in_beta = w["eg0.b"];
-        B.n_tiles = nt, B.part_s = ps, B.part_q = pq;
-        L.run("enc_gn_relu_a1", [&] { hipLaunchKernelGGL((gn_relu_stats_k<16, 512, 4>), dim3(g4, split_factor(g4, 8, 16, 1024)), dim3(256), 0, s, B); });
-        combine("enc_stats_a1", 8, 1.0 / 1024.0, S.a1m, S.a1r);
+        B.in = a["e_y1"], B.out = a["e_a1"], B.in_mean = P.S.y1m, B.in_rstd = P.S.y1r, B.in_gamma = w["eg0.w"], B.in_beta = w["eg0.b"];
+        B.n_tiles = nt, B.part_s = A.part_s, B.part_q = A.part_q;
+        P.L.run("enc_gn_relu_a1", [&] { hipLaunchKernelGGL((gn_relu_stats_k<16, 512, 4>), dim3(g4, psf), dim3(256), 0, P.s, B); });
+        combine(P, "enc_stats_a1", 8, 1.0 / 1024.0, P.S.a1m, P.S.a1r);
+        return;
     }
-    if (precision == VQHIP_PRECISION_BF16) {
-        launch_enc16_bf16(c, L, nt, s);
-    } else {
-        ConvArgs A{};
-        A.in = a["e_a1"], A.out = a["e_y4"], A.wfrag = w["r16c1.w"], A.bias_frag = w["r16c1.b"];
-        A.in_mean = S.a1m, A.in_rstd = S.a1r, A.in_gamma = w["r16g1.w"], A.in_beta = w["r16g1.b"], A.n_tiles = nt;
-        const int gq = (2 * nt + 3) / 4;
-        // conv1 carries the statistics.  This tensor's statistics blocks are its 128 output half rows: 2 x 1024 doubles per leaf of
-        // partials, which live in the region of conv2's output (e_a6: free until conv2 runs, after the combine)
-        double* psr = reinterpret_cast<double*>(a["e_a6"]);
-        double* pqr = psr + (size_t)nt * 128 * 8 * 32;
-        // a handful of tiles take two-row groups (32 ranges, half the serial chain per wave; same taps in the same order) — both convs:
-        // the statistics blocks are half rows, whatever the row grouping
-        const bool two = gq * 32 <= 512;   // up to 1024 leaves (measured)
-        const char* tab = two ? "steps.rowgroups8_2" : "steps.rowgroups8_4";
-        A.n_steps = c->nsteps[tab], A.grp_start = od(tab), A.part_s = psr, A.part_q = pqr;
-        L.run("enc_res16_conv1_s", [&] {
-            if (two) hipLaunchKernelGGL((conv8_c16_k<2, false, true>), dim3(gq, 32), dim3(256), 0, s, A, (const int4*)w[tab]);
-            else hipLaunchKernelGGL((conv8_c16_k<4, false, true>), dim3(gq, split_factor(gq, 8, 16, 1024)), dim3(256), 0, s, A, (const int4*)w[tab]);
-        });
-        L.run("enc_stats_y4", [&] { hipLaunchKernelGGL((gn_combine_k<false, true>), dim3(nt), dim3(8 * 32), 0, s, psr, pqr, S.y4m, S.y4r, 8, 1.0 / 1024.0); });
-        A.part_s = nullptr, A.part_q = nullptr;
-        A.in = a["e_y4"], A.out = a["e_a6"], A.wfrag = w["r16c2.w"], A.bias_frag = w["r16c2.b"], A.skip = a["e_a1"];
-        A.in_mean = S.y4m, A.in_rstd = S.y4r, A.in_gamma = w["r16g2.w"], A.in_beta = w["r16g2.b"];
-        L.run("enc_res16_conv2_s", [&] {
-            if (two) hipLaunchKernelGGL((conv8_c16_k<2, true, false>), dim3(gq, 32), dim3(256), 0, s, A, (const int4*)w[tab]);
-            else hipLaunchKernelGGL((conv8_c16_k<4, true, false>), dim3(gq, split_factor(gq, 8, 16, 1024)), dim3(256), 0, s, A, (const int4*)w[tab]);
-        });
-    }
-    {
-        ConvArgs A{};
-        A.in = a["e_a6"], A.out = a["e_x7"], A.wfrag = w["ed.w16"], A.bias_frag = w["ed.braw"], A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rows_k4s2_8"], A.n_taps = 64, A.grp_start = od("steps.rows_k4s2_8"), A.part_s = ps, A.part_q = pq;
-        const int psr = split_factor(gh, 4, 16, 512);
-        L.run("enc_down_s", [&] {
-            if (gh * psr * 2 <= 256) launch_rows<EncDownSplit2>(s, A, w["steps.rows_k4s2_8"], nt, psr);
-            else launch_rows<EncDownSplit>(s, A, w["steps.rows_k4s2_8"], nt, psr);
-        });
-        combine("enc_stats_x7", 8, 1.0 / 256.0, S.x7m, S.x7r);
-    }
-    {
-        ConvArgs A{};
-        A.in = a["e_x7"], A.out = a["e_y9"], A.wfrag = w["r32c1.w16"], A.bias_frag = w["r32c1.braw"];
-        A.in_mean = S.x7m, A.in_rstd = S.x7r, A.in_gamma = w["r32g1.w"], A.in_beta = w["r32g1.b"], A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27, A.grp_start = od("steps.rows_k3_4"), A.part_s = ps, A.part_q = pq;
-        const int psr = split_factor(gh, 4, 16, 512);
-        const bool ms = gh * psr * 2 <= 256;   // up to 1024 leaves (measured): also split the 32 couts over gridDim.z
-        L.run("enc_res32_conv1_s", [&] {
-            if (ms) launch_rows<EncR32C1Split2>(s, A, w["steps.rows_k3_4"], nt, psr);
-            else launch_rows<EncR32C1Split>(s, A, w["steps.rows_k3_4"], nt, psr);
-        });
-        combine("enc_stats_y9", 8, 1.0 / 256.0, S.y9m, S.y9r);
-        A.in = a["e_y9"], A.out = a["e_x11"], A.wfrag = w["r32c2.w16"], A.bias_frag = w["r32c2.braw"], A.skip = a["e_x7"];
-        A.in_mean = S.y9m, A.in_rstd = S.y9r, A.in_gamma = w["r32g2.w"], A.in_beta = w["r32g2.b"];
-        A.part_s = nullptr, A.part_q = nullptr, A.part_c = a["part_c"];
-        L.run("enc_res32_conv2_s", [&] {
-            if (ms) launch_rows<EncR32C2Split2>(s, A, w["steps.rows_k3_4"], nt, psr);
-            else launch_rows<EncR32C2Split>(s, A, w["steps.rows_k3_4"], nt, psr);
-        });
-        L.run("enc_csum_x11", [&] { hipLaunchKernelGGL((csum_combine_k<32>), dim3(nt), dim3(256), 0, s, a["part_c"], S.csum, w["efc0"], w["efc2"], a["gate"]); });
-    }
-    if (d_latent) {
-        launch_latent_assign(c, L, n, d_idx, d_latent, s, split_factor(g2, 8, 32, 512));
-        return L.rc;
-    }
-    VqArgs A{};
-    A.in = a["e_x11"], A.se_csum = S.csum, A.se_fc0 = w["efc0"], A.se_fc2 = w["efc2"];
-    A.epfrag = w["vq.ep"], A.ck_frag = w["vq.ck"], A.idx = d_idx, A.n_leaves = n, A.n_tiles = nt;
-    A.se_gate = a["gate"];   // computed once per tile by enc_csum_x11
-    L.run("enc_vq_s", [&] {
-        // mid-size batches: 8 tiles behind one copy of the folded codebook in LDS (33 KB) instead of 2
-        if (nt >= 256) hipLaunchKernelGGL(vq_folded_k<8>, dim3((nt + 7) / 8, split_factor((nt + 7) / 8, 2, 32, 512)), dim3(512), 0, s, A);
-        else hipLaunchKernelGGL(vq_folded_k<2>, dim3(g2, split_factor(g2, 8, 32, 2048)), dim3(128), 0, s, A);
+    // first conv twice: statistics pass, then recompute + GroupNorm(4,16) + ReLU + statistics for res.gn1.  Mid-size batches
+    // (split, nt >= 256) take it too, like the one-wave-per-tile path, instead of storing the raw output and normalising it in an
+    // elementwise pass (2 x 32 KiB per leaf less traffic)
+    A.out = y1;
+    if (!P.split) A.out_mean = P.S.y1m, A.out_rstd = P.S.y1r;
+    // first_roll: a wave per 16-leaf sub-tile with a rolling 3 x 3 row window in registers (three row loads per output row instead of nine)
+    // (the normalising pass only: its stores compete with the loads — 0.458 -> 0.393 ms; the statistics pass runs 0.322 ms on the
+    // (row, kd) kernel and 0.353 ms with the window, whose plane starts it cannot hide; VQHIP_FIRST=roll0 selects that as well)
+    const bool roll_stats = !P.split && c->first_roll_stats;
+    P.L.run(P.split ? "enc_conv_first_stats_s" : "enc_conv_first_stats", [&] {
+        if (P.raw && roll_stats) hipLaunchKernelGGL((conv_first_roll_k<0, true>), dim3(gq), dim3(256), 0, P.s, A);
+        else if (P.raw) hipLaunchKernelGGL((conv_first_k<0, 0, true>), dim3(g4, psf), dim3(256), 0, P.s, A, steps);
+        else if (roll_stats) hipLaunchKernelGGL(conv_first_roll_k<0>, dim3(gq), dim3(256), 0, P.s, A);
+        else hipLaunchKernelGGL(conv_first_k<0>, dim3(g4, psf), dim3(256), 0, P.s, A, steps);
     });
-    return L.rc;
+    if (P.split) combine(P, "enc_stats_y1", 4, 1.0 / 2048.0, P.S.y1m, P.S.y1r);
+    A.out = a["e_a1"], A.in_mean = P.S.y1m, A.in_rstd = P.S.y1r, A.in_gamma = w["eg0.w"], A.in_beta = w["eg0.b"];
+    if (!P.split) A.out_mean = P.S.a1m, A.out_rstd = P.S.a1r;
+    P.L.run(P.split ? "enc_conv_first_gn_s" : "enc_conv_first_gn", [&] {   // (rolling row window: vq_first_roll.h)
+        if (P.raw) hipLaunchKernelGGL((conv_first_roll_k<1, true>), dim3(gq, psf), dim3(256), 0, P.s, A);
+        else if (c->first_roll) hipLaunchKernelGGL(conv_first_roll_k<1>, dim3(gq, psf), dim3(256), 0, P.s, A);
+        else hipLaunchKernelGGL(conv_first_k<1>, dim3(g4, psf), dim3(256), 0, P.s, A, steps);
+    });
+    if (P.split) combine(P, "enc_stats_a1", 8, 1.0 / 1024.0, P.S.a1m, P.S.a1r);
+}
+
+// the 16-channel residual block: e_a1 (+ its statistics) -> e_y4 (+ gn2's statistics) -> e_a6.  On every path conv1 stores partials
+// of its output's statistics and a combine kernel finishes them.
+void enc_res16(EncPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt, gq = (2 * nt + 3) / 4;
+    if (P.precision == VQHIP_PRECISION_BF16) {
+        // ONE kernel per conv whatever the batch size and launch path, so a leaf's bits do not depend on the path.  conv1 stores the
+        // sixteen half-row totals per leaf and gn_combine_k<false> adds them in (oh, hw) order, as after conv8_lds_k.  The workgroups
+        // are persistent: grid from n_cus.
+        const int grid = std::min(4 * nt, c->n_cus);
+        e16b::Args B{};
+        B.in = a["e_a1"], B.out = a["e_y4"], B.wf = c->bf_r16c1, B.bias = w["r16c1.b"], B.n_groups = 4 * nt;
+        B.in_mean = P.S.a1m, B.in_rstd = P.S.a1r, B.in_gamma = w["r16g1.w"], B.in_beta = w["r16g1.b"];
+        B.part_s = part_s(c), B.part_q = part_q(c);
+        P.L.run("enc_res16_conv1_bf16", [&] { hipLaunchKernelGGL(e16b::conv_k<false>, dim3(grid), dim3(e16b::THREADS), e16b::LDS_BYTES, P.s, B); });
+        combine(P, "enc_stats_y4", 8, 1.0 / 1024.0, P.S.y4m, P.S.y4r);
+        B.in = a["e_y4"], B.out = a["e_a6"], B.wf = c->bf_r16c2, B.bias = w["r16c2.b"], B.skip = a["e_a1"];
+        B.in_mean = P.S.y4m, B.in_rstd = P.S.y4r, B.in_gamma = w["r16g2.w"], B.in_beta = w["r16g2.b"];
+        B.part_s = nullptr, B.part_q = nullptr;
+        P.L.run("enc_res16_conv2_bf16", [&] { hipLaunchKernelGGL(e16b::conv_k<true>, dim3(grid), dim3(e16b::THREADS), e16b::LDS_BYTES, P.s, B); });
+        return;
+    }
+    // lds: input planes staged in LDS by a persistent workgroup per CU; statistics as 16 half-row totals.  Otherwise the row-group kernel
+    const bool lds = !P.split && c->conv8_lds;
+    const int lds_grid = std::min(2 * nt, c->n_cus);
+    // a handful of tiles take two-row groups (32 ranges, half the serial chain per wave; same taps in the same order) — both convs:
+    // the statistics blocks are half rows, whatever the row grouping
+    const bool two = P.split && gq * 32 <= 512;   // up to 1024 leaves (measured)
+    const char* tab = two ? "steps.rowgroups8_2" : "steps.rowgroups8_4";
+    const int4* steps = (const int4*)w[tab];
+    const int psr = !P.split ? 1 : two ? 32 : split_factor(gq, 8, 16, 1024);
+    ConvArgs A{};
+    A.in = a["e_a1"], A.out = a["e_y4"], A.wfrag = w["r16c1.w"], A.bias_frag = w["r16c1.b"];
+    A.in_mean = P.S.a1m, A.in_rstd = P.S.a1r, A.in_gamma = w["r16g1.w"], A.in_beta = w["r16g1.b"], A.n_tiles = nt;
+    A.n_steps = c->nsteps[tab];
+    if (P.split) A.grp_start = grp(c, two ? "steps.rowgroups8_2.grp" : "steps.rowgroups8_4.grp");
+    if (lds) A.part_s = part_s(c), A.part_q = part_q(c);
+    else {
+        // conv1 carries the statistics.  The row-group kernel's statistics blocks are its 128 output half rows: 2 x 1024 doubles per leaf
+        // of partials, which live in the region of conv2's output (e_a6: free until conv2 runs, after the combine)
+        A.part_s = reinterpret_cast<double*>(a["e_a6"]), A.part_q = A.part_s + (size_t)nt * 128 * 8 * 32;
+    }
+    P.L.run(P.split ? "enc_res16_conv1_s" : "enc_res16_conv1", [&] {
+        if (lds && c->conv8_w16) hipLaunchKernelGGL((conv8_lds_k<false, true, 16, 0, false>), dim3(lds_grid), dim3(1024), LDS_CONV8, P.s, A);
+        else if (lds) hipLaunchKernelGGL((conv8_lds_k<false, true, 8, 0, true>), dim3(lds_grid), dim3(512), LDS_CONV8, P.s, A);
+        else if (two) hipLaunchKernelGGL((conv8_c16_k<2, false, true>), dim3(gq, psr), dim3(256), 0, P.s, A, steps);
+        else hipLaunchKernelGGL((conv8_c16_k<4, false, true>), dim3(gq, psr), dim3(256), 0, P.s, A, steps);
+    });
+    if (lds) combine(P, "enc_stats_y4", 8, 1.0 / 1024.0, P.S.y4m, P.S.y4r);
+    else combine_rows(P, "enc_stats_y4", A.part_s, A.part_q, P.S.y4m, P.S.y4r);
+    ConvArgs B{};
+    B.in = a["e_y4"], B.out = a["e_a6"], B.wfrag = w["r16c2.w"], B.bias_frag = w["r16c2.b"], B.skip = a["e_a1"];
+    B.in_mean = P.S.y4m, B.in_rstd = P.S.y4r, B.in_gamma = w["r16g2.w"], B.in_beta = w["r16g2.b"], B.n_tiles = nt;
+    B.n_steps = A.n_steps, B.grp_start = A.grp_start;
+    P.L.run(P.split ? "enc_res16_conv2_s" : "enc_res16_conv2", [&] {
+        if (lds && c->conv8_w16) hipLaunchKernelGGL((conv8_lds_k<true, false, 16, 0, false>), dim3(lds_grid), dim3(1024), LDS_CONV8, P.s, B);
+        else if (lds) hipLaunchKernelGGL((conv8_lds_k<true, false, 8, 0, true>), dim3(lds_grid), dim3(512), LDS_CONV8, P.s, B);
+        else if (two) hipLaunchKernelGGL((conv8_c16_k<2, true, false>), dim3(gq, psr), dim3(256), 0, P.s, B, steps);
+        else hipLaunchKernelGGL((conv8_c16_k<4, true, false>), dim3(gq, psr), dim3(256), 0, P.s, B, steps);
+    });
+}
+
+// down conv: e_a6 -> e_x7 with the statistics for res32.gn1
+void enc_down(EncPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt;
+    const float* steps = w["steps.rows_k4s2_8"];
+    ConvArgs A{};
+    A.in = a["e_a6"], A.out = a["e_x7"], A.wfrag = w["ed.w16"], A.bias_frag = w["ed.braw"], A.n_tiles = nt;
+    A.n_steps = c->nsteps["steps.rows_k4s2_8"], A.n_taps = 64;
+    if (!P.split) {
+        A.out_mean = P.S.x7m, A.out_rstd = P.S.x7r;
+        P.L.run("enc_down", [&] {
+            if (c->convdown_lds) hipLaunchKernelGGL(conv_down_lds_k<0>, dim3(std::min(2 * nt, c->n_cus)), dim3(1024), LDS_CONVDOWN, P.s, A);
+            else launch_rows<EncDownFull>(P.s, A, steps, nt);
+        });
+        return;
+    }
+    A.grp_start = grp(c, "steps.rows_k4s2_8.grp"), A.part_s = part_s(c), A.part_q = part_q(c);
+    const int gh = (2 * nt + 7) / 8, psr = split_factor(gh, 4, 16, 512);   // gh: workgroups of 8 half tiles (conv_rows16_k)
+    P.L.run("enc_down_s", [&] {
+        if (gh * psr * 2 <= 256) launch_rows<EncDownSplit2>(P.s, A, steps, nt, psr);
+        else launch_rows<EncDownSplit>(P.s, A, steps, nt, psr);
+    });
+    combine(P, "enc_stats_x7", 8, 1.0 / 256.0, P.S.x7m, P.S.x7r);
+}
+
+// the 32-channel residual block: e_x7 -> e_y9 (+ gn2's statistics) -> e_x11 with the channel sums of the attention
+void enc_res32(EncPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt;
+    const float* steps = w["steps.rows_k3_4"];
+    const int gh = (2 * nt + 7) / 8, psr = split_factor(gh, 4, 16, 512);
+    const bool ms = gh * psr * 2 <= 256;   // (split) up to 1024 leaves (measured): also split the 32 couts over gridDim.z
+    ConvArgs A{};
+    A.in = a["e_x7"], A.out = a["e_y9"], A.wfrag = w["r32c1.w16"], A.bias_frag = w["r32c1.braw"];
+    A.in_mean = P.S.x7m, A.in_rstd = P.S.x7r, A.in_gamma = w["r32g1.w"], A.in_beta = w["r32g1.b"], A.n_tiles = nt;
+    A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
+    ConvArgs B{};
+    B.in = a["e_y9"], B.out = a["e_x11"], B.wfrag = w["r32c2.w16"], B.bias_frag = w["r32c2.braw"], B.skip = a["e_x7"];
+    B.in_mean = P.S.y9m, B.in_rstd = P.S.y9r, B.in_gamma = w["r32g2.w"], B.in_beta = w["r32g2.b"], B.n_tiles = nt;
+    B.n_steps = A.n_steps, B.n_taps = 27;
+    if (!P.split) {
+        A.out_mean = P.S.y9m, A.out_rstd = P.S.y9r;
+        P.L.run("enc_res32_conv1", [&] {
+            if (c->conv4_lds) hipLaunchKernelGGL((conv4_lds_k<false, true, false, 0, 1>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV4, P.s, A);
+            else launch_rows<EncR32C1Full>(P.s, A, steps, nt);
+        });
+        B.out_csum = P.S.csum;
+        P.L.run("enc_res32_conv2", [&] {
+            if (c->conv4_lds) hipLaunchKernelGGL((conv4_lds_k<true, false, true, 0, 0>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV4, P.s, B);
+            else launch_rows<EncR32C2Full>(P.s, B, steps, nt);
+        });
+        return;
+    }
+    A.grp_start = B.grp_start = grp(c, "steps.rows_k3_4.grp");
+    A.part_s = part_s(c), A.part_q = part_q(c);
+    P.L.run("enc_res32_conv1_s", [&] {
+        if (ms) launch_rows<EncR32C1Split2>(P.s, A, steps, nt, psr);
+        else launch_rows<EncR32C1Split>(P.s, A, steps, nt, psr);
+    });
+    combine(P, "enc_stats_y9", 8, 1.0 / 256.0, P.S.y9m, P.S.y9r);
+    B.part_c = a["part_c"];
+    P.L.run("enc_res32_conv2_s", [&] {
+        if (ms) launch_rows<EncR32C2Split2>(P.s, B, steps, nt, psr);
+        else launch_rows<EncR32C2Split>(P.s, B, steps, nt, psr);
+    });
+    combine_csum<32>(P, "enc_csum_x11", P.S.csum, w["efc0"], w["efc2"]);
+}
+
+// training forward instead of the VQ: latent materialised, reference-faithful distance against the live codebook
+void enc_latent_assign(EncPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt;
+    P.L.run("train_codebook_frag", [&] { hipLaunchKernelGGL(codebook_frag_k, dim3(33), dim3(256), 0, P.s, w["cb"], w["tr.efrag"], w["tr.ee"]); });
+    LatentArgs A{};
+    A.in = a["e_x11"], A.se_csum = P.S.csum, A.se_fc0 = w["efc0"], A.se_fc2 = w["efc2"];
+    A.wproj = w["tr.wproj"], A.bproj = w["tr.bproj"], A.efrag = w["tr.efrag"], A.ee_frag = w["tr.ee"];
+    A.idx = P.d_idx, A.z = P.d_latent, A.z4 = P.latent_l4, A.n_leaves = P.n, A.n_tiles = nt;
+    const int split = P.split ? split_factor((nt + 1) / 2, 8, 32, 512) : 1;   // position ranges per tile
+    if (!P.split && nt >= 1024) P.L.run("train_latent_assign", [&] { hipLaunchKernelGGL(latent_assign_k<8>, dim3((nt + 7) / 8), dim3(512), LDS_LATENT, P.s, A); });
+    else if (P.split && nt >= 8) {
+        // small training batches: 144 KB of LDS = one workgroup per CU, so FOUR waves per workgroup (every SIMD busy; two left half of
+        // the CU idle) and twice the position ranges: 0.236 -> 0.13 ms at 2048 leaves
+        const int sp = std::min(64, 2 * split);
+        P.L.run("train_latent_assign", [&] { hipLaunchKernelGGL(latent_assign_k<4>, dim3((nt + 3) / 4, sp), dim3(256), LDS_LATENT, P.s, A); });
+    } else P.L.run("train_latent_assign", [&] { hipLaunchKernelGGL(latent_assign_k<2>, dim3((nt + 1) / 2, split), dim3(128), LDS_LATENT, P.s, A); });
+}
+
+// attention gates + projection + nearest code, folded: e_x11 -> indices
+void enc_vq(EncPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt, g2 = (nt + 1) / 2, g8 = (nt + 7) / 8;
+    VqArgs A{};
+    A.in = a["e_x11"], A.se_csum = P.S.csum, A.se_fc0 = w["efc0"], A.se_fc2 = w["efc2"];
+    A.epfrag = w["vq.ep"], A.ck_frag = w["vq.ck"], A.idx = P.d_idx, A.n_leaves = P.n, A.n_tiles = nt;
+    if (P.split) A.se_gate = a["gate"];   // computed once per tile by enc_csum_x11
+    P.L.run(P.split ? "enc_vq_s" : "enc_vq", [&] {
+        // one wave per tile: two position ranges per tile, 2 x n_tiles waves = 4 per SIMD on a full chunk (one wave per tile leaves 2,
+        // and the wave's MFMA chain -> argmin scan -> next chain sequence has nobody to overlap with)
+        if (!P.split) hipLaunchKernelGGL(vq_folded_k<8>, dim3(g8, c->vq_split), dim3(512), 0, P.s, A);
+        // mid-size batches: 8 tiles behind one copy of the folded codebook in LDS (33 KB) instead of 2
+        else if (nt >= 256) hipLaunchKernelGGL(vq_folded_k<8>, dim3(g8, split_factor(g8, 2, 32, 512)), dim3(512), 0, P.s, A);
+        else hipLaunchKernelGGL(vq_folded_k<2>, dim3(g2, split_factor(g2, 8, 32, 2048)), dim3(128), 0, P.s, A);
+    });
 }
 
 // precision: VQHIP_PRECISION_* of the two 16 -> 16 convs.  Only the plain encode entry points pass the handle's mode; the round
-// trip, every bounded, residual and size-sweep call, training and vqhip_multi_* take the default.
+// trip, every bounded, residual and size-sweep call, training and vqhip_multi_* take the default.  latent_l4: the forward of the
+// full training step (EncPass).
 int encode_chunk(vqhip_codec* c, const float* d_leaves, int64_t n, uint8_t* d_idx, hipStream_t s, float* d_latent = nullptr,
-                 int precision = VQHIP_PRECISION_FP32)
+                 int precision = VQHIP_PRECISION_FP32, float* latent_l4 = nullptr)
 {
     int rc = ensure_workspace(c, n);
     if (rc) return rc;
     if (precision == VQHIP_PRECISION_BF16 && (rc = ensure_enc_bf16_frags(c, s))) return rc;
     const int nt = (int)((n + 31) / 32);
-    auto& a = c->act;
-    auto& w = c->dw;
-    Launcher L{c, s, n};
-    const int g4 = (nt + 3) / 4, g8 = (nt + 7) / 8;
-    EncStats S = enc_stats_of(c);
-
-    // the position-major copy xt is only read by the training step (loss, first-conv weight gradients) and by debug fetches
-    float* xt = (c->training || c->full_training || c->debug) ? a["xt"] : nullptr;
     // raw: the first conv reads d_leaves itself; the row layout is still written when something else reads it (training, debug fetches, VQHIP_FIRST=steps' normalising pass)
     const bool raw = c->first_raw && c->first_roll && !c->training && !c->full_training;
-    c->cur_leaves = raw ? d_leaves : nullptr;
-    if (!raw || xt) L.run("pack_leaves", [&] { hipLaunchKernelGGL(pack_leaves_k, dim3(nt, nt <= 128 ? 8 : 1), dim3(256), 0, s, d_leaves, a["xr"], xt, n); });
-    if (use_split(c, nt, false)) return encode_chunk_split(c, L, n, d_idx, s, d_latent, precision);
-    if (c->first_once && !c->first_raw && !c->training && !c->full_training) {
-        // first conv once: conv + GroupNorm(4,16) + ReLU + statistics for res.gn1 out of the accumulators of a workgroup per 8-leaf group
-        ConvArgs A{};
-        A.in = a["xr"], A.out = a["e_a1"], A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"], A.in_gamma = w["eg0.w"], A.in_beta = w["eg0.b"];
-        A.out_mean = S.a1m, A.out_rstd = S.a1r, A.n_tiles = nt;
-        float* y1 = (c->debug || c->keep_y1) ? a["e_y1"] : nullptr;
-        L.run("enc_conv_first", [&] { hipLaunchKernelGGL(conv_first_once_k, dim3(std::min(4 * nt, c->n_cus)), dim3(512), 0, s, A, y1, S.y1m, S.y1r); });
-    } else {
-        // first conv twice: statistics pass, then recompute + GroupNorm(4,16) + ReLU + statistics for res.gn1
-        ConvArgs A{};
-        A.in = raw ? d_leaves : a["xr"], A.out = (c->debug || c->keep_y1) ? a["e_y1"] : nullptr, A.wfrag = w["e0.w"], A.bias_frag = w["e0.b"];
-        A.out_mean = S.y1m, A.out_rstd = S.y1r, A.n_tiles = nt, A.n_steps = c->nsteps["steps.rows8kd"], A.n_leaves = n;
-        // first_roll: a wave per 16-leaf sub-tile with a rolling 3 x 3 row window in registers (three row loads per output row instead of nine)
-        const int gq = (2 * nt + 3) / 4;
-        // (the normalising pass only: its stores compete with the loads — 0.458 -> 0.393 ms; the statistics pass runs 0.322 ms on the
-        // (row, kd) kernel and 0.353 ms with the window, whose plane starts it cannot hide; VQHIP_FIRST=roll0 selects that as well)
-        L.run("enc_conv_first_stats", [&] {
-            if (raw && c->first_roll_stats) hipLaunchKernelGGL((conv_first_roll_k<0, true>), dim3(gq), dim3(256), 0, s, A);
-            else if (raw) hipLaunchKernelGGL((conv_first_k<0, 0, true>), dim3(g4), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-            else if (c->first_roll_stats) hipLaunchKernelGGL(conv_first_roll_k<0>, dim3(gq), dim3(256), 0, s, A);
-            else hipLaunchKernelGGL(conv_first_k<0>, dim3(g4), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-        });
-        A.out = a["e_a1"], A.in_mean = S.y1m, A.in_rstd = S.y1r, A.in_gamma = w["eg0.w"], A.in_beta = w["eg0.b"];
-        A.out_mean = S.a1m, A.out_rstd = S.a1r;
-        L.run("enc_conv_first_gn", [&] {
-            if (raw) hipLaunchKernelGGL((conv_first_roll_k<1, true>), dim3(gq), dim3(256), 0, s, A);
-            else if (c->first_roll) hipLaunchKernelGGL(conv_first_roll_k<1>, dim3(gq), dim3(256), 0, s, A);
-            else hipLaunchKernelGGL(conv_first_k<1>, dim3(g4), dim3(256), 0, s, A, (const int4*)w["steps.rows8kd"]);
-        });
-    }
-    if (precision == VQHIP_PRECISION_BF16) launch_enc16_bf16(c, L, nt, s);
-    else {
-        ConvArgs A{};
-        A.in = a["e_a1"], A.out = a["e_y4"], A.wfrag = w["r16c1.w"], A.bias_frag = w["r16c1.b"];
-        A.in_mean = S.a1m, A.in_rstd = S.a1r, A.in_gamma = w["r16g1.w"], A.in_beta = w["r16g1.b"];
-        A.out_mean = S.y4m, A.out_rstd = S.y4r, A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rowgroups8_4"];
-        if (c->conv8_lds) {   // input planes staged in LDS by a persistent workgroup per CU; statistics as 16 half-row totals + combine
-            A.part_s = reinterpret_cast<double*>(a["part_s"]), A.part_q = reinterpret_cast<double*>(a["part_q"]);
-            if (c->conv8_w16) L.run("enc_res16_conv1", [&] { hipLaunchKernelGGL((conv8_lds_k<false, true, 16, 0, false>), dim3(std::min(2 * nt, c->n_cus)), dim3(1024), LDS_CONV8, s, A); });
-            else L.run("enc_res16_conv1", [&] { hipLaunchKernelGGL((conv8_lds_k<false, true, 8, 0, true>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV8, s, A); });
-            L.run("enc_stats_y4", [&] { hipLaunchKernelGGL((gn_combine_k<false>), dim3(nt), dim3(8 * 32), 0, s, A.part_s, A.part_q, S.y4m, S.y4r, 8, 1.0 / 1024.0); });
-        } else {   // row-group kernel: one partial per output half row (in the region of conv2's output, free until then), added row-major by the combine
-            A.part_s = reinterpret_cast<double*>(a["e_a6"]), A.part_q = A.part_s + (size_t)nt * 128 * 8 * 32;
-            L.run("enc_res16_conv1", [&] { hipLaunchKernelGGL((conv8_c16_k<4, false, true>), dim3((2 * nt + 3) / 4), dim3(256), 0, s, A, (const int4*)w["steps.rowgroups8_4"]); });
-            L.run("enc_stats_y4", [&] { hipLaunchKernelGGL((gn_combine_k<false, true>), dim3(nt), dim3(8 * 32), 0, s, A.part_s, A.part_q, S.y4m, S.y4r, 8, 1.0 / 1024.0); });
-        }
-    }
-    if (precision != VQHIP_PRECISION_BF16) {
-        ConvArgs A{};
-        A.in = a["e_y4"], A.out = a["e_a6"], A.wfrag = w["r16c2.w"], A.bias_frag = w["r16c2.b"], A.skip = a["e_a1"];
-        A.in_mean = S.y4m, A.in_rstd = S.y4r, A.in_gamma = w["r16g2.w"], A.in_beta = w["r16g2.b"], A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rowgroups8_4"];
-        if (c->conv8_lds && c->conv8_w16) L.run("enc_res16_conv2", [&] { hipLaunchKernelGGL((conv8_lds_k<true, false, 16, 0, false>), dim3(std::min(2 * nt, c->n_cus)), dim3(1024), LDS_CONV8, s, A); });
-        else if (c->conv8_lds) L.run("enc_res16_conv2", [&] { hipLaunchKernelGGL((conv8_lds_k<true, false, 8, 0, true>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV8, s, A); });
-        else L.run("enc_res16_conv2", [&] { hipLaunchKernelGGL((conv8_c16_k<4, true, false>), dim3((2 * nt + 3) / 4), dim3(256), 0, s, A, (const int4*)w["steps.rowgroups8_4"]); });
-    }
-    {
-        ConvArgs A{};
-        A.in = a["e_a6"], A.out = a["e_x7"], A.wfrag = w["ed.w16"], A.bias_frag = w["ed.braw"];
-        A.out_mean = S.x7m, A.out_rstd = S.x7r, A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rows_k4s2_8"], A.n_taps = 64;
-        if (c->convdown_lds) L.run("enc_down", [&] { hipLaunchKernelGGL(conv_down_lds_k<0>, dim3(std::min(2 * nt, c->n_cus)), dim3(1024), LDS_CONVDOWN, s, A); });
-        else L.run("enc_down", [&] { launch_rows<EncDownFull>(s, A, w["steps.rows_k4s2_8"], nt); });
-    }
-    {
-        ConvArgs A{};
-        A.in = a["e_x7"], A.out = a["e_y9"], A.wfrag = w["r32c1.w16"], A.bias_frag = w["r32c1.braw"];
-        A.in_mean = S.x7m, A.in_rstd = S.x7r, A.in_gamma = w["r32g1.w"], A.in_beta = w["r32g1.b"];
-        A.out_mean = S.y9m, A.out_rstd = S.y9r, A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-        if (c->conv4_lds) L.run("enc_res32_conv1", [&] { hipLaunchKernelGGL((conv4_lds_k<false, true, false, 0, 1>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV4, s, A); });
-        else L.run("enc_res32_conv1", [&] { launch_rows<EncR32C1Full>(s, A, w["steps.rows_k3_4"], nt); });
-    }
-    {
-        ConvArgs A{};
-        A.in = a["e_y9"], A.out = a["e_x11"], A.wfrag = w["r32c2.w16"], A.bias_frag = w["r32c2.braw"], A.skip = a["e_x7"];
-        A.in_mean = S.y9m, A.in_rstd = S.y9r, A.in_gamma = w["r32g2.w"], A.in_beta = w["r32g2.b"];
-        A.out_csum = S.csum, A.n_tiles = nt;
-        A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-        if (c->conv4_lds) L.run("enc_res32_conv2", [&] { hipLaunchKernelGGL((conv4_lds_k<true, false, true, 0, 0>), dim3(std::min(2 * nt, c->n_cus)), dim3(512), LDS_CONV4, s, A); });
-        else L.run("enc_res32_conv2", [&] { launch_rows<EncR32C2Full>(s, A, w["steps.rows_k3_4"], nt); });
-    }
-
-    if (d_latent) {
-        launch_latent_assign(c, L, n, d_idx, d_latent, s, 1);
-        return L.rc;
-    }
-    {
-        VqArgs A{};
-        A.in = a["e_x11"], A.se_csum = S.csum, A.se_fc0 = w["efc0"], A.se_fc2 = w["efc2"];
-        A.epfrag = w["vq.ep"], A.ck_frag = w["vq.ck"], A.idx = d_idx, A.n_leaves = n, A.n_tiles = nt;
-        // two position ranges per tile: 2 x n_tiles waves = 4 per SIMD on a full chunk (one wave per tile leaves 2, and the wave's
-        // MFMA chain -> argmin scan -> next chain sequence has nobody to overlap with)
-        const int vq_split = c->vq_split;
-        L.run("enc_vq", [&] { hipLaunchKernelGGL(vq_folded_k<8>, dim3(g8, vq_split), dim3(512), 0, s, A); });
-    }
-    return L.rc;
+    const bool train_forward = latent_l4 != nullptr;
+    EncPass P{{c, s, {c, s, n}, n, nt, use_split(c, nt, false), precision}, enc_stats_of(c, train_forward), d_leaves, raw, d_idx, d_latent, latent_l4, train_forward};
+    // the position-major copy xt is only read by the training step (loss, first-conv weight gradients) and by debug fetches
+    float* xt = (c->training || c->full_training || c->debug) ? c->act["xt"] : nullptr;
+    if (!raw || xt) P.L.run("pack_leaves", [&] { hipLaunchKernelGGL(pack_leaves_k, dim3(nt, nt <= 128 ? 8 : 1), dim3(256), 0, s, d_leaves, c->act["xr"], xt, n); });
+    enc_first(P);
+    enc_res16(P);
+    enc_down(P);
+    enc_res32(P);
+    if (d_latent) enc_latent_assign(P);
+    else enc_vq(P);
+    return P.L.rc;
 }
 
-// ---- bf16 decode mode (vqvdb_hip_precision.h; kernels in vq_dec64_bf16.h) ----
-// The bf16 A fragments of the two convs, packed on the device from the live fp32 fragments ("r64c1.w16", "r64c2.w16": uploaded at
-// create, rebuilt by refrag_all after every training update, which marks these stale).  Buffers first, so that a failed allocation
-// leaves the handle as it was.  The pack is followed by a wait: it happens once per weight change, and a later call may use
-// another stream.
-int ensure_bf16_frags(vqhip_codec* c, hipStream_t s)
+// ---- the decoder's stages: indices -> d2 -> y4 -> x6 (skip d2) -> voxels ----
+// decoder front: code gather + stem conv (a table lookup) + GroupNorm(8,64) + ReLU -> d_d2 with its statistics in st_b
+void dec_stem(DecPass& P)
 {
-    if (!c->bf_stale && c->bf_r64c1 && c->bf_r64c2) return VQHIP_OK;
-    int rc;
-    if ((rc = ensure(c, c->bf_r64c1, (size_t)d64b::FRAG_ELEMS, "the bf16 fragments of decoder.res_stack.0.conv1"))) return rc;
-    if ((rc = ensure(c, c->bf_r64c2, (size_t)d64b::FRAG_ELEMS, "the bf16 fragments of decoder.res_stack.0.conv2"))) return rc;
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(d64b::conv_k<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d64b::LDS_BYTES));
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(d64b::conv_k<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d64b::LDS_BYTES));
-    constexpr int wgs = (d64b::FRAG_ELEMS / 8 + 255) / 256;
-    hipLaunchKernelGGL(d64b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r64c1.w16"], c->bf_r64c1.get());
-    hipLaunchKernelGGL(d64b::frag_k, dim3(wgs), dim3(256), 0, s, c->dw["r64c2.w16"], c->bf_r64c2.get());
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(s));
-    c->bf_stale = false;
-    return VQHIP_OK;
-}
-
-// d_d2 (+ its statistics in st_b) -> d_y4 -> d_x6 with the statistics the tail needs, for any number of tiles: ONE kernel per conv
-// whatever the batch size, so a leaf's bits do not depend on the launch path.  Each conv stores per-block partials and the combine
-// kernels of the position-split path finish them (gn2 statistics into st_a; channel sums and attention gates).
-void launch_dec64_bf16(vqhip_codec* c, Launcher& L, int nt, hipStream_t s)
-{
-    auto& a = c->act;
-    auto& w = c->dw;
-    d64b::Args B{};
-    B.in = a["d_d2"], B.out = a["d_y4"], B.wf = c->bf_r64c1, B.bias = w["r64c1.braw"];
-    B.in_mean = a["st_b.mean"], B.in_rstd = a["st_b.rstd"], B.in_gamma = w["r64g1.w"], B.in_beta = w["r64g1.b"];
-    B.part_s = reinterpret_cast<double*>(a["part_s"]), B.part_q = reinterpret_cast<double*>(a["part_q"]);
-    L.run("dec_res64_conv1_bf16", [&] { hipLaunchKernelGGL(d64b::conv_k<false>, dim3(2 * nt), dim3(d64b::THREADS), d64b::LDS_BYTES, s, B); });
-    L.run("dec_stats_y4", [&] { hipLaunchKernelGGL(gn_combine_k<true>, dim3(nt), dim3(512), 0, s, B.part_s, B.part_q, a["st_a.mean"], a["st_a.rstd"], 8, 1.0 / 512.0); });
-    B.in = a["d_y4"], B.out = a["d_x6"], B.wf = c->bf_r64c2, B.bias = w["r64c2.braw"], B.skip = a["d_d2"];
-    B.in_mean = a["st_a.mean"], B.in_rstd = a["st_a.rstd"], B.in_gamma = w["r64g2.w"], B.in_beta = w["r64g2.b"];
-    B.part_s = nullptr, B.part_q = nullptr, B.part_c = a["part_c"];
-    L.run("dec_res64_conv2_bf16", [&] { hipLaunchKernelGGL(d64b::conv_k<true>, dim3(2 * nt), dim3(d64b::THREADS), d64b::LDS_BYTES, s, B); });
-    L.run("dec_csum_x6", [&] { hipLaunchKernelGGL((csum_combine_k<64>), dim3(nt), dim3(512), 0, s, a["part_c"], a["csum"], w["dfc0"], w["dfc2"], a["gate"]); });
-}
-
-// position-split decode for small batches (see encode_chunk_split)
-int decode_chunk_split(vqhip_codec* c, Launcher& L, const uint8_t* d_idx, int64_t n, float* d_out, hipStream_t s, int precision)
-{
-    const int nt = (int)((n + 31) / 32);
-    auto& a = c->act;
-    auto& w = c->dw;
-    auto od = [&](const char* name) { return reinterpret_cast<const int*>(w[std::string(name) + ".grp"]); };
-    const int g4 = (nt + 3) / 4, g2 = (nt + 1) / 2;
-    double* ps = reinterpret_cast<double*>(a["part_s"]);
-    double* pq = reinterpret_cast<double*>(a["part_q"]);
-    // fused statistics of split launches: per-block partials + gn_combine_k (16 slots = the 4-channel halves of GroupNorm(8,64))
-    auto combine64 = [&](const char* name, float* mean, float* rstd) {
-        L.run(name, [&] { hipLaunchKernelGGL(gn_combine_k<true>, dim3(nt), dim3(512), 0, s, ps, pq, mean, rstd, 8, 1.0 / 512.0); });
-    };
-    if (c->stem_fused && c->stem_taps && nt >= c->n_cus) {
-        // mid-size passes (a tile per CU and more): the decoder front as ONE kernel (table through the LDS ring, stem_taps_k) instead of
-        // gather + combine + normalise + combine; same d2 and statistics bit for bit
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt, g4 = (nt + 3) / 4;
+    const int4* steps = (const int4*)w["steps.k3s1_4"];
+    // one kernel: the table through the LDS ring (stem_taps_k) — on the split path for mid-size passes, a tile per CU and more — or
+    // gathered through the L1 by a workgroup per four leaves that normalises out of LDS and finishes both sets of statistics itself
+    // (stem_fused_k: at SOP-sized passes instead of four launches of 6-23 us each at 64 leaves).  Same d2 and statistics bit for bit
+    // as gather + combine + normalise + combine.
+    const bool taps = c->stem_fused && c->stem_taps && (!P.split || nt >= c->n_cus);
+    if (taps || (c->stem_fused && (!P.split || c->stem_small_fused))) {
         StemFusedArgs F{};
-        F.idx = d_idx, F.T = w["ds.lut"], F.bias = w["ds.b"], F.gamma = w["dg0.w"], F.beta = w["dg0.b"], F.d2 = a["d_d2"];
+        F.idx = P.d_idx, F.T = w["ds.lut"], F.bias = w["ds.b"], F.gamma = w["dg0.w"], F.beta = w["dg0.b"], F.d2 = a["d_d2"];
         F.out_mean = a["st_b.mean"], F.out_rstd = a["st_b.rstd"], F.ystem_dbg = c->debug ? a["d_ystem"] : nullptr;
-        F.n_leaves = n, F.n_tiles = nt;
-        L.run("dec_stem_gn_s", [&] { hipLaunchKernelGGL(k_stem_taps, dim3(std::min(nt, c->n_cus)), dim3(512), LDS_STEM_TAPS, s, F); });
-    } else if (c->stem_fused && c->stem_small_fused) {
-        // SOP-sized passes: the decoder front as ONE kernel too — a workgroup per four leaves gathers its table rows through the L1,
-        // normalises out of LDS and finishes both sets of statistics itself (stem_fused_k) — instead of gather + combine + normalise +
-        // combine (four launches of 6-23 us each at 64 leaves); same d2 and statistics bit for bit
-        StemFusedArgs F{};
-        F.idx = d_idx, F.T = w["ds.lut"], F.bias = w["ds.b"], F.gamma = w["dg0.w"], F.beta = w["dg0.b"], F.d2 = a["d_d2"];
-        F.out_mean = a["st_b.mean"], F.out_rstd = a["st_b.rstd"], F.ystem_dbg = c->debug ? a["d_ystem"] : nullptr;
-        F.steps = (const int4*)w["steps.k3s1_4"], F.grp_start = reinterpret_cast<const int*>(w["steps.k3s1_4.grp"]), F.n_steps = c->nsteps["steps.k3s1_4"];
-        F.n_leaves = n, F.n_tiles = nt;
-        L.run("dec_stem_gn_s", [&] {
-            if (nt <= 64) hipLaunchKernelGGL(stem_fused_k<16>, dim3(8 * nt), dim3(1024), 0, s, F);   // up to 2048 leaves: sixteen waves, half the gather chain each
-            else hipLaunchKernelGGL(stem_fused_k<8>, dim3(8 * nt), dim3(512), 0, s, F);
+        F.steps = steps, F.grp_start = grp(c, "steps.k3s1_4.grp"), F.n_steps = c->nsteps["steps.k3s1_4"];
+        F.n_leaves = P.n, F.n_tiles = nt;
+        P.L.run(P.split ? "dec_stem_gn_s" : "dec_stem_gn", [&] {
+            if (taps) hipLaunchKernelGGL(k_stem_taps, dim3(std::min(nt, c->n_cus)), dim3(512), LDS_STEM_TAPS, P.s, F);
+            else if (P.split && nt <= 64) hipLaunchKernelGGL(stem_fused_k<16>, dim3(8 * nt), dim3(1024), 0, P.s, F);   // up to 2048 leaves: sixteen waves, half the gather chain each
+            else hipLaunchKernelGGL(stem_fused_k<8>, dim3(8 * nt), dim3(512), 0, P.s, F);
         });
-    } else {
-        L.run("dec_stem_s", [&] {
-            hipLaunchKernelGGL(stem_lut_k, dim3(2 * nt, split_factor(2 * nt, 2, 16, 2048)), dim3(256), 0, s, d_idx, w["ds.lut"], w["ds.b"], a["d_ystem"], (float*)nullptr, (float*)nullptr,
-                               (const int4*)w["steps.k3s1_4"], c->nsteps["steps.k3s1_4"], n, nt, od("steps.k3s1_4"), ps, pq);
-        });
-        combine64("dec_stats_ystem", a["st_a.mean"], a["st_a.rstd"]);
-        {
-            ConvArgs A{};
-            A.in = a["d_ystem"], A.out = a["d_d2"], A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"];
-            A.in_gamma = w["dg0.w"], A.in_beta = w["dg0.b"], A.n_tiles = nt, A.part_s = ps, A.part_q = pq;
-            L.run("dec_gn_relu_d2", [&] { hipLaunchKernelGGL((gn_relu_stats_k<64, 64, 8>), dim3(g4, split_factor(g4, 2, 16, 1024)), dim3(256), 0, s, A); });
-        }
-        combine64("dec_stats_d2", a["st_b.mean"], a["st_b.rstd"]);
+        return;
     }
-    if (precision == VQHIP_PRECISION_BF16) {
-        launch_dec64_bf16(c, L, nt, s);
-    } else {
-        ConvArgs A{};
-        A.in = a["d_d2"], A.out = a["d_y4"], A.wfrag = w["r64c1.w"], A.bias_frag = w["r64c1.b"];
-        A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"], A.n_tiles = nt;
-        A.wfrag = w["r64c1.w16"], A.bias_frag = w["r64c1.braw"];
-        A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27, A.grp_start = od("steps.rows_k3_4");
-        A.part_s = ps, A.part_q = pq;
-        const int gh = (2 * nt + 7) / 8, psr = split_factor(gh, 4, 16, 512);   // 8 half tiles per workgroup, 16 output rows to split
-        const bool ms = gh * psr * 4 <= 1024;   // up to 2048 leaves (measured): also split the 64 couts over gridDim.z
-        const bool r64res = c->r64s_resident;
-        L.run("dec_res64_conv1_s", [&] {
-            if (ms && r64res) launch_rows<DecR64C1Split4Res>(s, A, w["steps.rows_k3_4"], nt, psr);
-            else if (ms) launch_rows<DecR64C1Split4>(s, A, w["steps.rows_k3_4"], nt, psr);
-            else launch_rows<DecR64C1Split>(s, A, w["steps.rows_k3_4"], nt, psr);
+    ConvArgs A{};
+    A.in = a["d_ystem"], A.out = a["d_d2"], A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"];
+    A.in_gamma = w["dg0.w"], A.in_beta = w["dg0.b"], A.n_tiles = nt;
+    if (!P.split) {
+        P.L.run("dec_stem", [&] {
+            hipLaunchKernelGGL(stem_lut_k, dim3(2 * nt), dim3(256), 0, P.s, P.d_idx, w["ds.lut"], w["ds.b"], a["d_ystem"], a["st_a.mean"], a["st_a.rstd"],
+                               steps, c->nsteps["steps.k3s1_4"], P.n, nt, (const int*)nullptr);
         });
-        combine64("dec_stats_y4", a["st_a.mean"], a["st_a.rstd"]);
-        A.in = a["d_y4"], A.out = a["d_x6"], A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.skip = a["d_d2"];
-        A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
-        A.part_s = nullptr, A.part_q = nullptr, A.part_c = a["part_c"];
-        L.run("dec_res64_conv2_s", [&] {
-            if (ms && r64res) launch_rows<DecR64C2Split4Res>(s, A, w["steps.rows_k3_4"], nt, psr);
-            else if (ms) launch_rows<DecR64C2Split4>(s, A, w["steps.rows_k3_4"], nt, psr);
-            else launch_rows<DecR64C2Split>(s, A, w["steps.rows_k3_4"], nt, psr);
-        });
-        L.run("dec_csum_x6", [&] { hipLaunchKernelGGL((csum_combine_k<64>), dim3(nt), dim3(512), 0, s, a["part_c"], a["csum"], w["dfc0"], w["dfc2"], a["gate"]); });
+        A.out_mean = a["st_b.mean"], A.out_rstd = a["st_b.rstd"];
+        P.L.run("dec_gn_relu_stats", [&] { hipLaunchKernelGGL((gn_relu_stats_k<64, 64, 8>), dim3(g4), dim3(256), 0, P.s, A); });
+        return;
     }
-    {
-        ConvArgs A{};
-        A.in = a["d_x6"], A.out = d_out, A.wfrag = w["tail.w"], A.bias_frag = w["tail.b"];
-        A.se_csum = a["csum"], A.se_fc0 = w["dfc0"], A.se_fc2 = w["dfc2"], A.n_tiles = nt, A.n_leaves = n;
-        A.n_steps = c->nsteps["steps.tail"], A.n_taps = 0, A.grp_start = od("steps.tail");
+    P.L.run("dec_stem_s", [&] {
+        hipLaunchKernelGGL(stem_lut_k, dim3(2 * nt, split_factor(2 * nt, 2, 16, 2048)), dim3(256), 0, P.s, P.d_idx, w["ds.lut"], w["ds.b"], a["d_ystem"], (float*)nullptr, (float*)nullptr,
+                           steps, c->nsteps["steps.k3s1_4"], P.n, nt, grp(c, "steps.k3s1_4.grp"), part_s(c), part_q(c));
+    });
+    combine_pairs(P, "dec_stats_ystem", a["st_a.mean"], a["st_a.rstd"]);
+    A.part_s = part_s(c), A.part_q = part_q(c);
+    P.L.run("dec_gn_relu_d2", [&] { hipLaunchKernelGGL((gn_relu_stats_k<64, 64, 8>), dim3(g4, split_factor(g4, 2, 16, 1024)), dim3(256), 0, P.s, A); });
+    combine_pairs(P, "dec_stats_d2", a["st_b.mean"], a["st_b.rstd"]);
+}
+
+// the 64-channel residual block: d_d2 (+ its statistics in st_b) -> d_y4 (gn2's statistics in st_a) -> d_x6 with the channel sums and
+// attention gates the tail needs
+void dec_res64(DecPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt;
+    if (P.precision == VQHIP_PRECISION_BF16) {
+        // ONE kernel per conv whatever the batch size, so a leaf's bits do not depend on the launch path.  Each conv stores per-block
+        // partials and the combine kernels of the position-split path finish them.
+        d64b::Args B{};
+        B.in = a["d_d2"], B.out = a["d_y4"], B.wf = c->bf_r64c1, B.bias = w["r64c1.braw"];
+        B.in_mean = a["st_b.mean"], B.in_rstd = a["st_b.rstd"], B.in_gamma = w["r64g1.w"], B.in_beta = w["r64g1.b"];
+        B.part_s = part_s(c), B.part_q = part_q(c);
+        P.L.run("dec_res64_conv1_bf16", [&] { hipLaunchKernelGGL(d64b::conv_k<false>, dim3(2 * nt), dim3(d64b::THREADS), d64b::LDS_BYTES, P.s, B); });
+        combine_pairs(P, "dec_stats_y4", a["st_a.mean"], a["st_a.rstd"]);
+        B.in = a["d_y4"], B.out = a["d_x6"], B.wf = c->bf_r64c2, B.bias = w["r64c2.braw"], B.skip = a["d_d2"];
+        B.in_mean = a["st_a.mean"], B.in_rstd = a["st_a.rstd"], B.in_gamma = w["r64g2.w"], B.in_beta = w["r64g2.b"];
+        B.part_s = nullptr, B.part_q = nullptr, B.part_c = a["part_c"];
+        P.L.run("dec_res64_conv2_bf16", [&] { hipLaunchKernelGGL(d64b::conv_k<true>, dim3(2 * nt), dim3(d64b::THREADS), d64b::LDS_BYTES, P.s, B); });
+        combine_csum<64>(P, "dec_csum_x6", a["csum"], w["dfc0"], w["dfc2"]);
+        return;
+    }
+    const float* steps = w["steps.rows_k3_4"];
+    ConvArgs A{};
+    A.in = a["d_d2"], A.out = a["d_y4"], A.wfrag = w["r64c1.w16"], A.bias_frag = w["r64c1.braw"];
+    A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"], A.n_tiles = nt;
+    A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
+    ConvArgs B{};
+    B.in = a["d_y4"], B.out = a["d_x6"], B.wfrag = w["r64c2.w16"], B.bias_frag = w["r64c2.braw"], B.skip = a["d_d2"];
+    B.in_mean = a["st_a.mean"], B.in_rstd = a["st_a.rstd"], B.in_gamma = w["r64g2.w"], B.in_beta = w["r64g2.b"], B.n_tiles = nt;
+    B.n_steps = A.n_steps, B.n_taps = 27;
+    if (!P.split) {
+        A.out_mean = a["st_a.mean"], A.out_rstd = a["st_a.rstd"];
+        P.L.run("dec_res64_conv1", [&] { launch_rows<DecR64C1Full>(P.s, A, steps, nt); });
+        B.out_csum = a["csum"];
+        P.L.run("dec_res64_conv2", [&] { launch_rows<DecR64C2Full>(P.s, B, steps, nt); });
+        return;
+    }
+    const int gh = (2 * nt + 7) / 8, psr = split_factor(gh, 4, 16, 512);   // 8 half tiles per workgroup, 16 output rows to split
+    const bool ms = gh * psr * 4 <= 1024;   // up to 2048 leaves (measured): also split the 64 couts over gridDim.z
+    const bool r64res = c->r64s_resident;
+    A.grp_start = B.grp_start = grp(c, "steps.rows_k3_4.grp");
+    A.part_s = part_s(c), A.part_q = part_q(c);
+    P.L.run("dec_res64_conv1_s", [&] {
+        if (ms && r64res) launch_rows<DecR64C1Split4Res>(P.s, A, steps, nt, psr);
+        else if (ms) launch_rows<DecR64C1Split4>(P.s, A, steps, nt, psr);
+        else launch_rows<DecR64C1Split>(P.s, A, steps, nt, psr);
+    });
+    combine_pairs(P, "dec_stats_y4", a["st_a.mean"], a["st_a.rstd"]);
+    B.part_c = a["part_c"];
+    P.L.run("dec_res64_conv2_s", [&] {
+        if (ms && r64res) launch_rows<DecR64C2Split4Res>(P.s, B, steps, nt, psr);
+        else if (ms) launch_rows<DecR64C2Split4>(P.s, B, steps, nt, psr);
+        else launch_rows<DecR64C2Split>(P.s, B, steps, nt, psr);
+    });
+    combine_csum<64>(P, "dec_csum_x6", a["csum"], w["dfc0"], w["dfc2"]);
+}
+
+// attention gates + up conv + final conv + sigmoid, folded: d_x6 -> voxels
+void dec_tail(DecPass& P)
+{
+    vqhip_codec* c = P.c;
+    auto &a = c->act, &w = c->dw;
+    const int nt = P.nt;
+    ConvArgs A{};
+    A.in = a["d_x6"], A.out = P.d_out, A.wfrag = w["tail.w"], A.bias_frag = w["tail.b"];
+    A.se_csum = a["csum"], A.se_fc0 = w["dfc0"], A.se_fc2 = w["dfc2"], A.n_tiles = nt, A.n_leaves = P.n;
+    A.n_steps = c->nsteps["steps.tail"], A.n_taps = 0;
+    if (P.split) {
+        A.grp_start = grp(c, "steps.tail.grp");
         A.se_gate = a["gate"];   // computed once per tile by dec_csum_x6
         // a few tiles: sixteen waves per (tile, slab) on the 16x16x4 MFMA (a quarter of the serial chain per wave)
-        const int t16 = c->tail16_tiles;
-        if (nt <= t16) {
+        if (nt <= c->tail16_tiles) {
             A.wfrag = w["tail.w16"], A.bias_frag = w["tail.braw"];
-            L.run("dec_tail_s", [&] { hipLaunchKernelGGL(tail_small16_k<4>, dim3(nt, 4, 4), dim3(256), 0, s, A); });
+            P.L.run("dec_tail_s", [&] { hipLaunchKernelGGL(tail_small16_k<4>, dim3(nt, 4, 4), dim3(256), 0, P.s, A); });
         } else {
-            L.run("dec_tail_s", [&] { hipLaunchKernelGGL(tail_small_k<false>, dim3(nt, 4), dim3(256), 0, s, A); });
+            P.L.run("dec_tail_s", [&] { hipLaunchKernelGGL(tail_small_k<false>, dim3(nt, 4), dim3(256), 0, P.s, A); });
         }
+    } else if (c->tail_rows) {
+        A.wfrag = c->tail_groups ? w["tail.wgroups"] : w["tail.wrows"], A.bias_frag = w["tail.braw"];
+        if (c->tail_groups) P.L.run("dec_tail_groups", [&] { hipLaunchKernelGGL(tail_groups16_k<0>, dim3((2 * nt + 7) / 8), dim3(512), LDS_TAIL_GROUPS, P.s, A); });
+        else if (c->tail_rows32) P.L.run("dec_tail_rows32", [&] { hipLaunchKernelGGL(tail_rows32_k<0>, dim3((nt + 3) / 4), dim3(256), LDS_TAIL_ROWS, P.s, A); });
+        else P.L.run("dec_tail", [&] { hipLaunchKernelGGL(tail_rows16_k<0>, dim3((2 * nt + 7) / 8), dim3(512), LDS_TAIL_ROWS, P.s, A); });
+    } else {
+        P.L.run("dec_tail_slab", [&] { launch_mfma32<DecTailSlab>(P.s, A, w["steps.tail"], nt); });
     }
-    return L.rc;
 }
 
 // precision: VQHIP_PRECISION_* of the two 64 -> 64 convs.  Only the plain decode entry points pass the handle's mode; every call that
@@ -1570,71 +1624,13 @@ int decode_chunk(vqhip_codec* c, const uint8_t* d_idx, int64_t n, float* d_out, 
 {
     int rc = ensure_workspace(c, n);
     if (rc) return rc;
+    if (precision == VQHIP_PRECISION_BF16 && (rc = ensure_dec_bf16_frags(c, s))) return rc;
     const int nt = (int)((n + 31) / 32);
-    auto& a = c->act;
-    auto& w = c->dw;
-    Launcher L{c, s, n};
-    const int g4 = (nt + 3) / 4;
-
-    if (precision == VQHIP_PRECISION_BF16 && (rc = ensure_bf16_frags(c, s))) return rc;
-    if (use_split(c, nt, true)) return decode_chunk_split(c, L, d_idx, n, d_out, s, precision);
-    if (c->stem_fused) {   // gather + stem + GroupNorm + ReLU + statistics in one kernel: the stem output stays in LDS
-        StemFusedArgs F{};
-        F.idx = d_idx, F.T = w["ds.lut"], F.bias = w["ds.b"], F.gamma = w["dg0.w"], F.beta = w["dg0.b"], F.d2 = a["d_d2"];
-        F.out_mean = a["st_b.mean"], F.out_rstd = a["st_b.rstd"], F.ystem_dbg = c->debug ? a["d_ystem"] : nullptr;
-        F.steps = (const int4*)w["steps.k3s1_4"], F.grp_start = reinterpret_cast<const int*>(w["steps.k3s1_4.grp"]), F.n_steps = c->nsteps["steps.k3s1_4"];
-        F.n_leaves = n, F.n_tiles = nt;
-        if (c->stem_taps) L.run("dec_stem_gn", [&] { hipLaunchKernelGGL(k_stem_taps, dim3(std::min(nt, c->n_cus)), dim3(512), LDS_STEM_TAPS, s, F); });
-        else L.run("dec_stem_gn", [&] { hipLaunchKernelGGL(stem_fused_k<8>, dim3(8 * nt), dim3(512), 0, s, F); });
-    } else {
-        L.run("dec_stem", [&] {
-            hipLaunchKernelGGL(stem_lut_k, dim3(2 * nt), dim3(256), 0, s, d_idx, w["ds.lut"], w["ds.b"], a["d_ystem"], a["st_a.mean"], a["st_a.rstd"],
-                               (const int4*)w["steps.k3s1_4"], c->nsteps["steps.k3s1_4"], n, nt, (const int*)nullptr);
-        });
-        {
-            ConvArgs A{};
-            A.in = a["d_ystem"], A.out = a["d_d2"], A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"];
-            A.in_gamma = w["dg0.w"], A.in_beta = w["dg0.b"], A.out_mean = a["st_b.mean"], A.out_rstd = a["st_b.rstd"], A.n_tiles = nt;
-            L.run("dec_gn_relu_stats", [&] { hipLaunchKernelGGL((gn_relu_stats_k<64, 64, 8>), dim3(g4), dim3(256), 0, s, A); });
-        }
-    }
-    if (precision == VQHIP_PRECISION_BF16) {
-        launch_dec64_bf16(c, L, nt, s);
-    } else {
-        {
-            ConvArgs A{};
-            A.in = a["d_d2"], A.out = a["d_y4"], A.wfrag = w["r64c1.w"], A.bias_frag = w["r64c1.b"];
-            A.in_mean = a["st_b.mean"], A.in_rstd = a["st_b.rstd"], A.in_gamma = w["r64g1.w"], A.in_beta = w["r64g1.b"];
-            A.out_mean = a["st_a.mean"], A.out_rstd = a["st_a.rstd"], A.n_tiles = nt;
-            A.wfrag = w["r64c1.w16"], A.bias_frag = w["r64c1.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-            L.run("dec_res64_conv1", [&] { launch_rows<DecR64C1Full>(s, A, w["steps.rows_k3_4"], nt); });
-        }
-        {
-            ConvArgs A{};
-            A.in = a["d_y4"], A.out = a["d_x6"], A.wfrag = w["r64c2.w"], A.bias_frag = w["r64c2.b"], A.skip = a["d_d2"];
-            A.in_mean = a["st_a.mean"], A.in_rstd = a["st_a.rstd"], A.in_gamma = w["r64g2.w"], A.in_beta = w["r64g2.b"];
-            A.out_csum = a["csum"], A.n_tiles = nt;
-            A.wfrag = w["r64c2.w16"], A.bias_frag = w["r64c2.braw"], A.n_steps = c->nsteps["steps.rows_k3_4"], A.n_taps = 27;
-            L.run("dec_res64_conv2", [&] { launch_rows<DecR64C2Full>(s, A, w["steps.rows_k3_4"], nt); });
-        }
-    }
-    {
-        ConvArgs A{};
-        A.in = a["d_x6"], A.out = d_out, A.wfrag = w["tail.w"], A.bias_frag = w["tail.b"];
-        A.se_csum = a["csum"], A.se_fc0 = w["dfc0"], A.se_fc2 = w["dfc2"], A.n_tiles = nt, A.n_leaves = n;
-        A.n_steps = c->nsteps["steps.tail"], A.n_taps = 0;
-        if (c->tail_rows) {
-            A.wfrag = w["tail.wrows"], A.bias_frag = w["tail.braw"];
-            if (c->tail_groups) {
-                A.wfrag = w["tail.wgroups"];
-                L.run("dec_tail_groups", [&] { hipLaunchKernelGGL(tail_groups16_k<0>, dim3((2 * nt + 7) / 8), dim3(512), LDS_TAIL_GROUPS, s, A); });
-            } else if (c->tail_rows32) L.run("dec_tail_rows32", [&] { hipLaunchKernelGGL(tail_rows32_k<0>, dim3((nt + 3) / 4), dim3(256), LDS_TAIL_ROWS, s, A); });
-            else L.run("dec_tail", [&] { hipLaunchKernelGGL(tail_rows16_k<0>, dim3((2 * nt + 7) / 8), dim3(512), LDS_TAIL_ROWS, s, A); });
-        } else {
-            L.run("dec_tail_slab", [&] { launch_mfma32<DecTailSlab>(s, A, w["steps.tail"], nt); });
-        }
-    }
-    return L.rc;
+    DecPass P{{c, s, {c, s, n}, n, nt, use_split(c, nt, true), precision}, d_idx, d_out};
+    dec_stem(P);
+    dec_res64(P);
+    dec_tail(P);
+    return P.L.rc;
 }
 
 int ensure_io(vqhip_codec* c, int64_t n)
@@ -2459,7 +2455,7 @@ int vqhip_set_decode_mode(vqhip_codec* c, int mode)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (mode == VQHIP_PRECISION_BF16)
-        if (int rc = ensure_bf16_frags(c, c->stream)) return rc;   // (a failed allocation: VQHIP_ERR_NOMEM, the mode as it was)
+        if (int rc = ensure_dec_bf16_frags(c, c->stream)) return rc;   // (a failed allocation: VQHIP_ERR_NOMEM, the mode as it was)
     c->decode_precision = mode;
     return VQHIP_OK;
 }

@@ -69,7 +69,7 @@ int refrag_all(vqhip_codec* c, hipStream_t s)
 {
     int rc;
     float* d;
-    c->bf_stale = true;   // the bf16 decode mode packs its fragments from "r64c1.w16" / "r64c2.w16" again at its next call (ensure_bf16_frags)
+    c->bf_stale = true;   // the bf16 decode mode packs its fragments from "r64c1.w16" / "r64c2.w16" again at its next call (ensure_dec_bf16_frags)
     c->bf_enc_stale = true;   // ... and the bf16 encode mode its own from "r16c1.w" / "r16c2.w" (ensure_enc_bf16_frags)
     // The job list is built once (the tables are allocated on the first pass and never move, the parameters live in ft_P) and kept on the
     // device; every later call is ONE launch of refrag_multi_k.
@@ -306,12 +306,8 @@ int fulltrain_forward(vqhip_codec* c, const float* d_leaves, int64_t n, hipStrea
         fold_done = c->ft_ev[c->ft_ev_next++];
         HIPCHK(c, hipEventRecord(fold_done, ws));
     }
-    c->keep_y1 = true;
-    c->z4_out = c->act["t_z"];
-    rc = encode_chunk(c, d_leaves, n, c->tr_idx, s, c->tr_z);   // encoder + latent (flat rows and L4) + assignment against the live codebook
-    c->keep_y1 = false;
-    c->z4_out = nullptr;
-    if (rc) return rc;
+    // encoder + latent (flat rows, and the L4 layout in t_z) + assignment against the live codebook
+    if ((rc = encode_chunk(c, d_leaves, n, c->tr_idx, s, c->tr_z, VQHIP_PRECISION_FP32, c->act["t_z"]))) return rc;
     const int nt = (int)((n + 31) / 32);
     auto& a = c->act;
     auto& w = c->dw;
