@@ -2,7 +2,7 @@
  * vqvdb_hip_vec3_active.h — compact records for the quantised residuals of a vqhip_vec3_codec handle: records
  * that hold only the ACTIVE voxels of a leaf, and a decode side that knows the mask.  The masked calls of vqvdb_hip_vec3_mask.h
  * write a record of 512 voxels whatever the mask; here a record shrinks with the leaf's active count, and apply can write a
- * background into the inactive voxels.  In memory only: there is no Vec3 file container.  The scalar handle has no such calls.
+ * background into the inactive voxels.  On disk: the .vqv3 container of vqvdb_hip_vec3_file.h.  The scalar handle has no such calls.
  *
  * Mask.  As in vqvdb_hip_vec3_mask.h: uint64 [n][8], little endian, bit L of word j of a leaf is voxel 64 j + L, one bit for the
  * three channels of its voxel; device masks are 8-byte aligned.  Encode and decode must be given the same masks.

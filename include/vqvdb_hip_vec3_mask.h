@@ -2,7 +2,7 @@
  * vqvdb_hip_vec3_mask.h — active-voxel masks for the quantised residuals of a vqhip_vec3_codec handle (the
  * scalar handle has no masked calls).  Only the encode side knows a
  * mask: a masked encode produces ordinary codes and records, and vqhip_vec3_residual_apply_device and
- * vqhip_vec3_residual_decompress read them unchanged.  In memory only: there is no Vec3 file container.
+ * vqhip_vec3_residual_decompress read them unchanged.  These calls work in memory; on disk: vqvdb_hip_vec3_file.h.
  *
  * Mask.  uint64 [n][8], little endian.  Bit L of word j of a leaf is voxel 64 j + L (the words of OpenVDB's NodeMask<3>,
  * leaf.valueMask(), unconverted); one bit covers the three channels of its voxel.  Device masks are 8-byte aligned.

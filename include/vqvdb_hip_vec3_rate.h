@@ -4,7 +4,7 @@
  * many bytes?"; these calls answer the converse: the histogram of the leaves over their record sizes at up to
  * VQHIP_VEC3_RATE_MAX_TOLS tolerances ("rungs") in one pass over them, from which the payload of a compress at each rung follows
  * to the byte, and a compress that picks the tightest rung whose payload fits a budget.  No call, kernel or format of the other
- * headers changes.  In memory only: there is no Vec3 file container, hence no sidecar size.
+ * headers changes.  These calls work in memory (on disk: vqvdb_hip_vec3_file.h); there is no sidecar, hence no sidecar size.
  *
  * Histogram: int64 [n_tols][VQHIP_VEC3_RATE_CLASSES], row t for tols[t].  Column s = 0 .. 48 counts the quantised leaves whose
  * code b0 | b1 << 5 | b2 << 10 has s = b0 + b1 + b2 planes (a record of 64 * s bytes), column 49 the raw leaves

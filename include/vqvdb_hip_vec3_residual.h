@@ -3,7 +3,7 @@
  * Vec3 model).  vqvdb_hip_vec3_bounded.h keeps max |x - x~| <= tol by naming every leaf over the tolerance, which
  * the caller then stores raw (6144 bytes); these calls store x - x^ of such a leaf on a grid of 1.875 * tol instead, a few bits
  * per value with one bit width per channel, and keep a leaf raw only where that grid cannot hold it.  The calls of
- * vqvdb_hip_vec3_bounded.h are unchanged.  In memory only: there is no Vec3 file container.
+ * vqvdb_hip_vec3_bounded.h are unchanged.  These calls work in memory; on disk: vqvdb_hip_vec3_file.h.
  *
  * A leaf is [512][3] float32, voxel-major and channels last, as everywhere on this handle.
  *

@@ -157,6 +157,10 @@ MASK_WORDS = 8   # VQHIP_VEC3_MASK_WORDS: uint64 words of one leaf's mask, bit L
 VEC3_ACTIVE_SYMBOLS = ["vqhip_vec3_active_record_bytes", "vqhip_vec3_active_encode_device", "vqhip_vec3_active_apply_device",
                        "vqhip_vec3_active_sweep_device", "vqhip_vec3_active_compress", "vqhip_vec3_active_decompress",
                        "vqhip_vec3_active_sweep"]
+# every symbol include/vqvdb_hip_vec3_file.h declares (leaf-pointer calls and the .vqv3 container of the Vec3 handle; kept apart from the lists above)
+VEC3_FILE_SYMBOLS = ["vqhip_vec3_encode_leaves", "vqhip_vec3_decode_leaves", "vqhip_vec3_file_compress", "vqhip_vec3_file_compress_active",
+                     "vqhip_vec3_file_decompress", "vqhip_vec3_file_info"]
+VEC3_LEAF_FLOATS = 1536   # one Vec3f leaf buffer: [512][3] float32
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
 
@@ -196,6 +200,22 @@ class _GridSource(ctypes.Structure):
                 ("origins", ctypes.c_void_p), ("n_leaves", ctypes.c_int64)]
 
 
+class _Vec3GridSource(ctypes.Structure):
+    """vqhip_vec3_grid_source"""
+    _fields_ = [("name", ctypes.c_char_p), ("transform", ctypes.c_void_p), ("leaf_ptrs", ctypes.c_void_p), ("origins", ctypes.c_void_p),
+                ("n_leaves", ctypes.c_int64), ("masks", ctypes.c_void_p), ("background", ctypes.c_void_p)]
+
+
+class _Vec3GridInfo(ctypes.Structure):
+    """vqhip_vec3_grid_info"""
+    _fields_ = [("name", ctypes.c_char_p), ("transform", ctypes.c_float * 16), ("num_codes", ctypes.c_uint32), ("total_blocks", ctypes.c_uint64),
+                ("grid_index", ctypes.c_int), ("kind", ctypes.c_int), ("mode", ctypes.c_int), ("tol", ctypes.c_float),
+                ("has_background", ctypes.c_int), ("background", ctypes.c_float * 3)]
+
+
+VEC3_GRID_BEGIN_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(_Vec3GridInfo))
+VEC3_LEAF_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint64),
+                                      ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p))
 GRID_BEGIN_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(_GridInfo))
 LEAF_ALLOC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64,
                                  ctypes.POINTER(ctypes.c_void_p))
@@ -394,6 +414,16 @@ def load_library() -> ctypes.CDLL:
     lib.vqhip_vec3_active_sweep.argtypes = [vp, vp, vp, i64, vp, ci, vp]
     for name in VEC3_ACTIVE_SYMBOLS:
         getattr(lib, name).restype = i64 if name.endswith("_bytes") else ci
+    # include/vqvdb_hip_vec3_file.h
+    lib.vqhip_vec3_encode_leaves.argtypes = [vp, vp, i64, vp]
+    lib.vqhip_vec3_decode_leaves.argtypes = [vp, vp, i64, vp]
+    lib.vqhip_vec3_file_compress.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(_Vec3GridSource), ci, i64, ctypes.POINTER(StreamStats)]
+    lib.vqhip_vec3_file_compress_active.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(_Vec3GridSource), ci, cf, i64, ctypes.POINTER(StreamStats), vp]
+    lib.vqhip_vec3_file_decompress.argtypes = [vp, ctypes.c_char_p, i64, VEC3_GRID_BEGIN_FN, VEC3_LEAF_ALLOC_FN, vp, ctypes.POINTER(StreamStats)]
+    lib.vqhip_vec3_file_info.argtypes = [ctypes.c_char_p, ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ci), ctypes.POINTER(ci),
+                                         ctypes.POINTER(cf), ctypes.POINTER(i64), ctypes.POINTER(i64)]
+    for name in VEC3_FILE_SYMBOLS:
+        getattr(lib, name).restype = ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -994,6 +1024,126 @@ class HipVec3Codec:
         self._check(self._lib.vqhip_vec3_active_sweep(self._h, leaves.ctypes.data, masks.ctypes.data, leaves.shape[0], tols.ctypes.data, len(tols),
                                                       out.ctypes.data))
         return out
+
+    # ---- OpenVDB leaves and the .vqv3 container: include/vqvdb_hip_vec3_file.h ----
+    @staticmethod
+    def _leaf_ptrs(leaf_arrays: Sequence[np.ndarray], n: int, writable: bool) -> np.ndarray:
+        """uint64 [n]: the addresses of n per-leaf buffers, each checked: float32, 1536 elements, C-contiguous (the library reads /
+        writes 6 KiB each)."""
+        if len(leaf_arrays) != n:
+            raise ValueError(f"expected {n} leaf buffers, got {len(leaf_arrays)}")
+        for i, a in enumerate(leaf_arrays):
+            if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.size != VEC3_LEAF_FLOATS or not a.flags.c_contiguous \
+                    or (writable and not a.flags.writeable):
+                raise ValueError(f"leaf buffer {i}: need a C-contiguous{' writable' if writable else ''} float32 array of {VEC3_LEAF_FLOATS} elements")
+        return np.array([a.ctypes.data for a in leaf_arrays], dtype=np.uint64)
+
+    def encode_leaves(self, leaf_arrays: Sequence[np.ndarray]) -> np.ndarray:
+        """Leaf-pointer entry point: one [512,3] float32 buffer per leaf (e.g. the buffers of a Vec3fGrid's leaves) -> indices [n,64]."""
+        n = len(leaf_arrays)
+        ptrs = self._leaf_ptrs(leaf_arrays, n, writable=False)
+        idx = np.empty((n, 64), dtype=np.uint16)
+        self._check(self._lib.vqhip_vec3_encode_leaves(self._h, ptrs.ctypes.data, n, idx.ctypes.data))
+        return idx
+
+    def decode_leaves(self, indices: np.ndarray, leaf_arrays: Sequence[np.ndarray]) -> None:
+        indices = self.check_indices(indices)
+        n = indices.shape[0]
+        ptrs = self._leaf_ptrs(leaf_arrays, n, writable=True)
+        self._check(self._lib.vqhip_vec3_decode_leaves(self._h, indices.ctypes.data, n, ptrs.ctypes.data))
+
+    def _grid_sources(self, grids, need_masks: bool):
+        """(vqhip_vec3_grid_source array, its length, the arrays it points into) of the file calls' grid dicts: "name", "origins" int32
+        [n,3], "leaves" (float32 [n,512,3] or a list of n [512,3] buffers), optional "transform" (16 floats), "masks" (bool [n,512] or
+        uint64 [n,8]; required by compress_file_active) and "background" (three numbers)."""
+        n_g = len(grids)
+        src = (_Vec3GridSource * max(n_g, 1))()
+        keep = []
+        for i, g in enumerate(grids):
+            origins = np.ascontiguousarray(g["origins"], dtype=np.int32).reshape(-1, 3)
+            n = origins.shape[0]
+            leaves = g["leaves"]
+            if isinstance(leaves, np.ndarray):
+                leaves = self.check_leaves(leaves)
+                if leaves.shape[0] != n:
+                    raise ValueError(f"grid {i}: {n} origins but {leaves.shape[0]} leaves")
+                ptrs = np.ascontiguousarray(leaves.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(VEC3_LEAF_FLOATS * 4), dtype=np.uint64)
+            else:
+                ptrs = self._leaf_ptrs(leaves, n, writable=False)
+            masks = g.get("masks")
+            if masks is None and need_masks:
+                raise ValueError(f"grid {i}: compress_file_active needs masks")
+            if masks is not None:
+                masks = check_masks(pack_masks(masks) if isinstance(masks, np.ndarray) and masks.dtype == np.bool_ else masks, n)
+            tr = None if g.get("transform") is None else np.ascontiguousarray(g["transform"], dtype=np.float32).reshape(16)
+            bg = self.check_background(g.get("background"))
+            bname = g["name"].encode()
+            keep += [origins, leaves, ptrs, masks, tr, bg, bname]
+            src[i].name = bname
+            src[i].transform = None if tr is None else tr.ctypes.data
+            src[i].leaf_ptrs = ptrs.ctypes.data if n else None
+            src[i].origins = origins.ctypes.data if n else None
+            src[i].n_leaves = n
+            src[i].masks = masks.ctypes.data if masks is not None and n else None
+            src[i].background = None if bg is None else bg.ctypes.data
+        return src, n_g, keep
+
+    def compress_file(self, path, grids, batch_leaves: int = 0) -> dict:
+        """Whole-file compress into a .vqv3 file of kind 0 (origins and the indices of encode; masks are not written).  grids: the
+        dicts of _grid_sources.  Returns the stream statistics."""
+        src, n_g, _keep = self._grid_sources(grids, need_masks=False)
+        st = StreamStats()
+        self._check(self._lib.vqhip_vec3_file_compress(self._h, os.fspath(path).encode(), src, n_g, batch_leaves, ctypes.byref(st)))
+        return st.as_dict()
+
+    def compress_file_active(self, path, grids, tol: float, batch_leaves: int = 0) -> dict:
+        """Whole-file compress into a .vqv3 file of kind 1: per grid what compress_active gives on its leaves and masks, in the
+        handle's precision mode, which the header records.  Returns the stream statistics and "payload_bytes", one per grid."""
+        tol = self.check_tol(tol)
+        src, n_g, _keep = self._grid_sources(grids, need_masks=True)
+        st, pb = StreamStats(), np.zeros(max(n_g, 1), dtype=np.int64)
+        self._check(self._lib.vqhip_vec3_file_compress_active(self._h, os.fspath(path).encode(), src, n_g, tol, batch_leaves, ctypes.byref(st),
+                                                              pb.ctypes.data))
+        return dict(st.as_dict(), payload_bytes=[int(b) for b in pb[:n_g]])
+
+    def decompress_file(self, path, batch_leaves: int = 0, return_stats: bool = False):
+        """Whole-file decompress of a .vqv3 file of either kind -> a list of dicts, one per grid: "name", "transform" [16], "origins"
+        [n,3], "masks" uint64 [n,8] (None for kind 0), "leaves" float32 [n,512,3], "batches" (the sizes of the leaf_alloc batches) and
+        the info fields "num_codes", "total_blocks", "kind", "mode", "tol", "background" (None where the grid has none).  The leaf
+        allocator hands out one fresh block per batch, the stand-in for tree.touchLeaf().  return_stats: -> (grids, statistics)."""
+        grids = []
+
+        def on_grid(_user, gi):
+            g = gi.contents
+            grids.append({"name": g.name.decode(), "transform": np.array(g.transform[:], dtype=np.float32), "num_codes": int(g.num_codes),
+                          "total_blocks": int(g.total_blocks), "kind": int(g.kind), "mode": int(g.mode),
+                          "tol": float(g.tol),
+                          "background": np.array(g.background[:], dtype=np.float32) if g.has_background else None, "_blocks": []})
+            return 0
+
+        def on_alloc(_user, gidx, origins, masks, n, out_ptrs):
+            try:
+                org = np.ctypeslib.as_array(origins, shape=(n, 3)).copy()
+                msk = np.ctypeslib.as_array(masks, shape=(n, MASK_WORDS)).copy() if masks else None
+                buf = np.empty((n, 512, 3), dtype=np.float32)
+                dst = np.ctypeslib.as_array(ctypes.cast(out_ptrs, ctypes.POINTER(ctypes.c_uint64)), shape=(n,))
+                dst[:] = buf.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(VEC3_LEAF_FLOATS * 4)
+                grids[gidx]["_blocks"].append((org, msk, buf))
+                return 0
+            except Exception as e:  # noqa: BLE001 — an exception must not unwind through the C frames
+                print(f"decompress_file allocator: {e}", file=sys.stderr)
+                return 1
+
+        cb_g, cb_a = VEC3_GRID_BEGIN_FN(on_grid), VEC3_LEAF_ALLOC_FN(on_alloc)
+        st = StreamStats()
+        self._check(self._lib.vqhip_vec3_file_decompress(self._h, os.fspath(path).encode(), batch_leaves, cb_g, cb_a, None, ctypes.byref(st)))
+        for g in grids:
+            bl = g.pop("_blocks")
+            g["batches"] = [len(b[0]) for b in bl]
+            g["origins"] = np.concatenate([b[0] for b in bl]) if bl else np.zeros((0, 3), np.int32)
+            g["masks"] = None if g["kind"] == 0 else (np.concatenate([b[1] for b in bl]) if bl else np.zeros((0, MASK_WORDS), np.uint64))
+            g["leaves"] = np.concatenate([b[2] for b in bl]) if bl else np.zeros((0, 512, 3), np.float32)
+        return (grids, st.as_dict()) if return_stats else grids
 
     # ---- full training: include/vqvdb_hip_vec3_fulltrain.h ----
     @staticmethod
@@ -1800,6 +1950,18 @@ def vec3_active_record_bytes(code: int, active: int) -> int:
     if size < 0:
         raise ValueError(f"code 0x{int(code) & 0xFFFFFFFF:X} with {active} active voxels has no record size")
     return size
+
+
+def vec3_file_info(path) -> dict:
+    """vqhip_vec3_file_info: the header fields of a .vqv3 file after the whole-file length check; no handle, no GPU."""
+    lib = load_library()
+    ng, k, kind, mode, tol = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_int(), ctypes.c_int(), ctypes.c_float()
+    blocks, pay = ctypes.c_int64(), ctypes.c_int64()
+    if lib.vqhip_vec3_file_info(os.fspath(path).encode(), ctypes.byref(ng), ctypes.byref(k), ctypes.byref(kind), ctypes.byref(mode), ctypes.byref(tol),
+                                ctypes.byref(blocks), ctypes.byref(pay)) != 0:
+        raise RuntimeError(lib.vqhip_vec3_last_error(None).decode())
+    return {"n_grids": ng.value, "num_codes": k.value, "kind": kind.value, "mode": mode.value, "tol": tol.value, "total_blocks": blocks.value,
+            "payload_bytes": pay.value}
 
 
 class HipMultiCodec:

@@ -46,6 +46,8 @@ struct vqhip_vec3_codec {
     DevBuf<uint64_t> mk_mask;
     // compact records (vq_vec3_active.inc), host sweep: the payload bytes of every rung [64]
     DevBuf<int64_t> ac_bytes;
+    // leaf-pointer and file calls (vq_vec3_file.inc): pinned staging of one batch's leaves [m][512][3]
+    PinBuf<float> fl_stage;
     struct Dbg {
         DevBuf<float> p;
         int64_t n = 0;
@@ -477,6 +479,38 @@ int v3_prepare(vqhip_vec3_codec* c)
     return VQHIP_OK;
 }
 
+// one chunk of the host entry points (m <= c->chunk, after v3_prepare): host leaves -> host indices and back, in the handle's mode
+int v3_encode_host_chunk(vqhip_vec3_codec* c, const float* leaves, int64_t m, uint16_t* indices)
+{
+    if (int rc = v3_ensure_io(c, m)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->io_leaves, leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    if (int rc = v3_encode_mode(c, c->io_leaves, m, c->io_idx, c->stream)) return rc;
+    HIPCHK(c, hipMemcpyAsync(indices, c->io_idx, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VQHIP_OK;
+}
+
+int v3_decode_host_chunk(vqhip_vec3_codec* c, const uint16_t* indices, int64_t m, float* leaves)
+{
+    if (int rc = v3_ensure_io(c, m)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->io_idx, indices, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+    if (int rc = v3_decode_mode(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
+    HIPCHK(c, hipMemcpyAsync(leaves, c->io_leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VQHIP_OK;
+}
+
+// the decoder gathers codebook rows by index: every one of n leaves' indices is below K, or nothing is launched.  first_leaf: the
+// position of indices[0] in the caller's array, for the message
+int v3_check_indices(vqhip_vec3_codec* c, const uint16_t* indices, int64_t n, int64_t first_leaf)
+{
+    for (int64_t i = 0; i < n * 64; ++i)
+        if (indices[i] >= c->k_codes)
+            return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decode: index " + std::to_string(indices[i]) + " at leaf " + std::to_string(first_leaf + i / 64) +
+                                                     ", position " + std::to_string(i % 64) + " is out of range (num_codes " + std::to_string(c->k_codes) + ")");
+    return VQHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -598,14 +632,8 @@ int vqhip_vec3_encode(vqhip_vec3_codec* c, const float* leaves, int64_t n, uint1
     if (n == 0) return VQHIP_OK;
     if (!leaves || !indices) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 encode: null pointer");
     if (int rc = v3_prepare(c)) return rc;
-    for (int64_t o = 0; o < n; o += c->chunk) {
-        const int64_t m = std::min(c->chunk, n - o);
-        if (int rc = v3_ensure_io(c, m)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->io_leaves, leaves + o * 1536, (size_t)m * 1536 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (int rc = v3_encode_mode(c, c->io_leaves, m, c->io_idx, c->stream)) return rc;
-        HIPCHK(c, hipMemcpyAsync(indices + o * 64, c->io_idx, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    for (int64_t o = 0; o < n; o += c->chunk)
+        if (int rc = v3_encode_host_chunk(c, leaves + o * 1536, std::min(c->chunk, n - o), indices + o * 64)) return rc;
     return VQHIP_OK;
 }
 
@@ -615,19 +643,10 @@ int vqhip_vec3_decode(vqhip_vec3_codec* c, const uint16_t* indices, int64_t n, f
     if (n < 0) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decode: n_leaves < 0");
     if (n == 0) return VQHIP_OK;
     if (!leaves || !indices) return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decode: null pointer");
-    for (int64_t i = 0; i < n * 64; ++i)
-        if (indices[i] >= c->k_codes)
-            return v3_fail(c, VQHIP_ERR_INVALID, "vec3 decode: index " + std::to_string(indices[i]) + " at leaf " + std::to_string(i / 64) +
-                                                     ", position " + std::to_string(i % 64) + " is out of range (num_codes " + std::to_string(c->k_codes) + ")");
+    if (int rc = v3_check_indices(c, indices, n, 0)) return rc;
     if (int rc = v3_prepare(c)) return rc;
-    for (int64_t o = 0; o < n; o += c->chunk) {
-        const int64_t m = std::min(c->chunk, n - o);
-        if (int rc = v3_ensure_io(c, m)) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->io_idx, indices + o * 64, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
-        if (int rc = v3_decode_mode(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
-        HIPCHK(c, hipMemcpyAsync(leaves + o * 1536, c->io_leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
+    for (int64_t o = 0; o < n; o += c->chunk)
+        if (int rc = v3_decode_host_chunk(c, indices + o * 64, std::min(c->chunk, n - o), leaves + o * 1536)) return rc;
     return VQHIP_OK;
 }
 

@@ -46,6 +46,46 @@ inline int v3a_popcount(const uint64_t* words)
     return a;
 }
 
+// one chunk of vqhip_vec3_active_compress (m <= c->chunk, after v3_prepare), host arrays of that chunk: the round trip, the masked
+// error, the compact encode; its records go to payload + *total, which grows by their bytes
+int v3a_compress_chunk(vqhip_vec3_codec* c, const char* what, const float* leaves, const uint64_t* masks, int64_t m, float tol, uint16_t* indices,
+                       float* leaf_err, uint16_t* leaf_code, uint8_t* payload, int64_t* total)
+{
+    int rc = v3m_roundtrip_host(c, leaves, masks, 0, m);
+    if (!rc) rc = v3a_encode(c, c->io_leaves, c->rs_recon, c->mk_mask, c->rs_err, m, tol, c->rs_code, c->rs_off, c->rs_payload, m * 6144, c->stream);
+    if (rc) {
+        hipStreamSynchronize(c->stream);   // the copies above may still read the caller's arrays
+        return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(indices, c->io_idx, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    if (leaf_err)
+        HIPCHK(c, hipMemcpyAsync(leaf_err, c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return v3r_fetch_chunk(c, what, 0, m, leaf_code, payload, total);   // sized by offsets[m]
+}
+
+// one chunk of vqhip_vec3_active_decompress (m <= c->chunk, after v3_prepare), host arrays of that chunk whose codes and sizes have
+// been checked; payload addresses the chunk's first record and *bytes receives the bytes of its records
+int v3a_decompress_chunk(vqhip_vec3_codec* c, const uint16_t* indices, const uint64_t* masks, int64_t m, float tol, const uint16_t* leaf_code,
+                         const uint8_t* payload, const float* background, float* leaves, std::vector<int64_t>& off, int64_t* bytes)
+{
+    if (int rc = v3_ensure_io(c, m)) return rc;
+    if (int rc = v3m_ensure_host(c, m)) return rc;
+    off.resize((size_t)m + 1);
+    off[0] = 0;
+    for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + vqa::record_bytes(leaf_code[i], v3a_popcount(masks + i * 8));
+    HIPCHK(c, hipMemcpy(c->io_idx, indices, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->mk_mask, masks, (size_t)m * 64, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->rs_code, leaf_code, (size_t)m * sizeof(uint16_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->rs_off, off.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
+    if (off[m] > 0) HIPCHK(c, hipMemcpy(c->rs_payload, payload, (size_t)off[m], hipMemcpyHostToDevice));
+    *bytes = off[m];
+    if (int rc = v3_decode_mode(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
+    if (int rc = v3a_apply(c, c->io_leaves, c->mk_mask, m, tol, c->rs_code, c->rs_off, c->rs_payload, background, c->stream)) return rc;
+    HIPCHK(c, hipMemcpyAsync(leaves, c->io_leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VQHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -108,17 +148,9 @@ int vqhip_vec3_active_compress(vqhip_vec3_codec* c, const float* leaves, const u
     int64_t total = 0;
     for (int64_t o = 0; o < n; o += c->chunk) {
         const int64_t m = std::min(c->chunk, n - o);
-        int rc = v3m_roundtrip_host(c, leaves, masks, o, m);
-        if (!rc) rc = v3a_encode(c, c->io_leaves, c->rs_recon, c->mk_mask, c->rs_err, m, tol, c->rs_code, c->rs_off, c->rs_payload, m * 6144, c->stream);
-        if (rc) {
-            hipStreamSynchronize(c->stream);   // the copies above may still read the caller's arrays
+        if (int rc = v3a_compress_chunk(c, "vec3 active_compress", leaves + o * 1536, masks + o * 8, m, tol, indices + o * 64,
+                                        leaf_err ? leaf_err + o * VQHIP_VEC3_ERR_FLOATS : nullptr, leaf_code + o, payload, &total))
             return rc;
-        }
-        HIPCHK(c, hipMemcpyAsync(indices + o * 64, c->io_idx, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
-        if (leaf_err)
-            HIPCHK(c, hipMemcpyAsync(leaf_err + o * VQHIP_VEC3_ERR_FLOATS, c->rs_err, (size_t)m * VQHIP_VEC3_ERR_FLOATS * sizeof(float),
-                                     hipMemcpyDeviceToHost, c->stream));
-        if ((rc = v3r_fetch_chunk(c, "vec3 active_compress", o, m, leaf_code, payload, &total))) return rc;   // sized by offsets[m]
     }
     *payload_bytes = total;
     return VQHIP_OK;
@@ -147,24 +179,13 @@ int vqhip_vec3_active_decompress(vqhip_vec3_codec* c, const uint16_t* indices, c
                                                  " payload bytes, the caller gives " + std::to_string(payload_bytes));
     if (int rc = v3_prepare(c)) return rc;
     std::vector<int64_t> off;
-    int64_t at = 0;
+    int64_t at = 0, bytes = 0;
     for (int64_t o = 0; o < n; o += c->chunk) {
         const int64_t m = std::min(c->chunk, n - o);
-        if (int rc = v3_ensure_io(c, m)) return rc;
-        if (int rc = v3m_ensure_host(c, m)) return rc;
-        off.resize((size_t)m + 1);
-        off[0] = 0;
-        for (int64_t i = 0; i < m; ++i) off[i + 1] = off[i] + vqa::record_bytes(leaf_code[o + i], v3a_popcount(masks + (o + i) * 8));
-        HIPCHK(c, hipMemcpy(c->io_idx, indices + o * 64, (size_t)m * 64 * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->mk_mask, masks + o * 8, (size_t)m * 64, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->rs_code, leaf_code + o, (size_t)m * sizeof(uint16_t), hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->rs_off, off.data(), (size_t)(m + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
-        if (off[m] > 0) HIPCHK(c, hipMemcpy(c->rs_payload, payload + at, (size_t)off[m], hipMemcpyHostToDevice));
-        at += off[m];
-        if (int rc = v3_decode_mode(c, c->io_idx, m, c->io_leaves, c->stream)) return rc;
-        if (int rc = v3a_apply(c, c->io_leaves, c->mk_mask, m, tol, c->rs_code, c->rs_off, c->rs_payload, background, c->stream)) return rc;
-        HIPCHK(c, hipMemcpyAsync(leaves + o * 1536, c->io_leaves, (size_t)m * 1536 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (int rc = v3a_decompress_chunk(c, indices + o * 64, masks + o * 8, m, tol, leaf_code + o, payload + at, background, leaves + o * 1536, off,
+                                          &bytes))
+            return rc;
+        at += bytes;
     }
     return VQHIP_OK;
 }

@@ -231,3 +231,172 @@ def save_residual_v2(path, tol: float, grids) -> None:
 def load_residual_v2(path):
     with open(path, "rb") as f:
         return loads_residual_v2(f.read())
+
+
+# ---- `.vqv3` v1: the Vec3 codec's container (include/vqvdb_hip_vec3_file.h) ----
+#     file : "VQVEC3" | u8 version=1 | u8 numGrids (1..255) | u32 numCodes | u8 kind | u8 mode | u16 zero | f32 tol | u32 zero
+#     grid : u32 nameLength | name | f32 transform[16] | u16 latentShape[3]={4,4,4} | u32 totalBlocks (n) | u8 hasBackground | u8 zero[3]
+#            f32 background[3] | u64 payloadBytes | i32 origins[n][3] | u16 indices[n][64]
+#            kind 1 only: u64 masks[n][8] | u16 codes[n] | u8 payload[payloadBytes]
+# kind 0: indices only (mode 0, tol +0.0, payloadBytes 0).  kind 1: masks and the compact records of include/vqvdb_hip_vec3_active.h;
+# mode is the decoder mode the records belong to (0 fp32, 1 bf16).  A leaf's record starts at the exclusive sum of the sizes before it.
+VEC3_MAGIC = b"VQVEC3"
+VEC3_VERSION = 1
+VEC3_HEADER_BYTES = 24
+VEC3_KIND_INDICES, VEC3_KIND_ACTIVE = 0, 1
+VEC3_CODE_KEPT, VEC3_CODE_RAW = 0xFFFE, 0xFFFF
+
+
+def vec3_record_bytes(codes, active) -> np.ndarray:
+    """int64 [n]: the bytes of every leaf's compact record from its code and its count of active voxels: 0 kept, 8 ceil(3 A / 2) raw,
+    8 ceil(A / 64) (b0 + b1 + b2) quantised.  A code that is neither a sentinel nor three widths of 0..16 raises."""
+    c = np.asarray(codes).astype(np.int64).reshape(-1)
+    a = np.asarray(active).astype(np.int64).reshape(-1)
+    if len(c) != len(a):
+        raise ValueError(f"{len(c)} codes but {len(a)} active counts")
+    if len(a) and (a.min() < 0 or a.max() > 512):
+        raise ValueError("an active count is outside 0..512")
+    kept, raw = c == VEC3_CODE_KEPT, c == VEC3_CODE_RAW
+    b = [(c >> s) & 31 for s in (0, 5, 10)]
+    bad = ~(kept | raw) & ((c < 0) | ((c >> 15) != 0) | (b[0] > 16) | (b[1] > 16) | (b[2] > 16))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f".vqv3: code 0x{int(c[i]) & 0xFFFF:04X} of leaf {i} is neither 0xFFFE, 0xFFFF nor three widths of 0..16")
+    return np.where(kept, 0, np.where(raw, 8 * ((3 * a + 1) // 2), 8 * ((a + 63) // 64) * (b[0] + b[1] + b[2])))
+
+
+def _vec3_popcounts(masks) -> np.ndarray:
+    return np.unpackbits(np.ascontiguousarray(masks).view(np.uint8).reshape(len(masks), 64), axis=1).sum(axis=1, dtype=np.int64)
+
+
+def dumps_vec3(header: dict, grids) -> bytes:
+    """header: {"num_codes", "kind", and for kind 1 "mode" (0 / 1) and "tol"}.  grids: dicts with "name", "origins" int32 [n,3],
+    "indices" uint16 [n,64], optional "transform" (16 floats, default identity) and "background" (three floats or None), and for
+    kind 1 "masks" uint64 [n,8], "codes" uint16 [n] and "payload" (bytes or uint8 array)."""
+    kind, num_codes = int(header["kind"]), int(header["num_codes"])
+    if kind not in (VEC3_KIND_INDICES, VEC3_KIND_ACTIVE):
+        raise ValueError(f".vqv3: kind {kind} is neither 0 nor 1")
+    mode = int(header.get("mode", 0)) if kind else 0
+    if mode not in (0, 1):
+        raise ValueError(f".vqv3: mode {mode} is neither 0 (fp32) nor 1 (bf16)")
+    if not 1 <= num_codes <= 65536:
+        raise ValueError(f".vqv3: numCodes {num_codes} is not in 1..65536")
+    if not 1 <= len(grids) <= 255:
+        raise ValueError("a .vqv3 file holds 1..255 grids")
+    with np.errstate(over="ignore"):
+        tol = np.float32(header.get("tol", 0.0)) if kind else np.float32(0.0)
+    out = [VEC3_MAGIC + struct.pack("<BBIBBH", VEC3_VERSION, len(grids), num_codes, kind, mode, 0) + np.array([tol], "<f4").tobytes() + struct.pack("<I", 0)]
+    for g in grids:
+        origins = np.ascontiguousarray(g["origins"], dtype="<i4").reshape(-1, 3)
+        n = len(origins)
+        if n >= 1 << 32:
+            raise ValueError("more than 2^32-1 leaves in one grid")
+        indices = np.ascontiguousarray(g["indices"], dtype="<u2").reshape(n, 64)
+        name = g["name"].encode() if isinstance(g["name"], str) else bytes(g["name"])
+        transform = IDENTITY if g.get("transform") is None else np.asarray(g["transform"], dtype="<f4").reshape(16)
+        bg = g.get("background")
+        bg_bytes = b"\0" * 12 if bg is None else np.ascontiguousarray(bg, dtype="<f4").reshape(3).tobytes()
+        payload = b""
+        if kind:
+            masks = np.ascontiguousarray(g["masks"], dtype="<u8").reshape(n, 8)
+            codes = np.ascontiguousarray(g["codes"], dtype="<u2").reshape(n)
+            payload = np.ascontiguousarray(g["payload"], dtype=np.uint8).tobytes() if isinstance(g["payload"], np.ndarray) else bytes(g["payload"])
+            need = int(vec3_record_bytes(codes, _vec3_popcounts(masks)).sum())
+            if need != len(payload):
+                raise ValueError(f".vqv3: grid '{name.decode(errors='replace')}': the codes and masks need {need} payload bytes, got {len(payload)}")
+        out.append(struct.pack("<I", len(name)) + name + transform.tobytes() + struct.pack("<3HIB3x", 4, 4, 4, n, 0 if bg is None else 1) + bg_bytes +
+                   struct.pack("<Q", len(payload)))
+        out += [origins.tobytes(), indices.tobytes()]
+        if kind:
+            out += [masks.tobytes(), codes.tobytes(), payload]
+    return b"".join(out)
+
+
+def loads_vec3(buf):
+    """-> (header dict, [grid dict]) with the keys of dumps_vec3 ("background" None where absent; kind 0: "masks", "codes" and
+    "payload" None).  Refuses whatever the C reader refuses: wrong magic, version, kind, mode, reserved fields, a length that is not
+    what the headers imply, an index >= numCodes, an illegal code, record sizes that do not sum to payloadBytes."""
+    buf = bytes(buf)
+    if len(buf) < VEC3_HEADER_BYTES:
+        raise ValueError("Failed to read file header.")
+    if buf[:6] != VEC3_MAGIC:
+        raise ValueError("Invalid file magic; not a .vqv3 file.")
+    version, n_grids, num_codes, kind, mode, zero16 = struct.unpack_from("<BBIBBH", buf, 6)
+    tol_bits, zero32 = struct.unpack_from("<II", buf, 16)
+    if version != VEC3_VERSION:
+        raise ValueError(f"Unsupported .vqv3 version {version} (expected 1).")
+    if n_grids < 1:
+        raise ValueError(".vqv3: a file holds 1..255 grids, the header says 0")
+    if not 1 <= num_codes <= 65536:
+        raise ValueError(f".vqv3: numCodes {num_codes} is not in 1..65536")
+    if kind not in (VEC3_KIND_INDICES, VEC3_KIND_ACTIVE):
+        raise ValueError(f".vqv3: kind {kind} is neither 0 nor 1")
+    if mode > 1:
+        raise ValueError(f".vqv3: mode {mode} is neither 0 (fp32) nor 1 (bf16)")
+    if zero16 or zero32:
+        raise ValueError(".vqv3: a reserved field of the file header is not zero")
+    if kind == VEC3_KIND_INDICES and (mode or tol_bits):
+        raise ValueError(".vqv3: a file of kind 0 carries mode 0 and tol +0.0")
+    header = {"num_codes": num_codes, "kind": kind, "mode": mode, "tol": float(np.frombuffer(buf, "<f4", 1, 16)[0])}
+    off, grids = VEC3_HEADER_BYTES, []
+    trunc = ".vqv3: file truncated inside the metadata of a grid"
+    for _ in range(n_grids):
+        if off + 4 > len(buf):
+            raise ValueError(trunc)
+        (name_len,) = struct.unpack_from("<I", buf, off); off += 4
+        if off + name_len + 98 > len(buf):
+            raise ValueError(trunc)
+        name = buf[off:off + name_len].decode(); off += name_len
+        transform = np.frombuffer(buf, "<f4", 16, off).copy(); off += 64
+        s0, s1, s2, n, has_bg, z0, z1, z2 = struct.unpack_from("<3HI4B", buf, off); off += 14
+        bg_raw = buf[off:off + 12]; off += 12
+        (payload_bytes,) = struct.unpack_from("<Q", buf, off); off += 8
+        who = f".vqv3: grid '{name}' "
+        if (s0, s1, s2) != (4, 4, 4):
+            raise ValueError(who + f"has latent shape [{s0},{s1},{s2}], not [4,4,4]")
+        if has_bg > 1 or z0 or z1 or z2:
+            raise ValueError(who + "has a hasBackground byte above 1 or a reserved byte that is not zero")
+        if not has_bg and bg_raw != b"\0" * 12:
+            raise ValueError(who + "has no background but background values that are not +0.0")
+        if kind == VEC3_KIND_INDICES and payload_bytes:
+            raise ValueError(who + f"belongs to a file of kind 0 but has payloadBytes {payload_bytes}")
+        fixed = n * (12 + 128 + (64 + 2 if kind else 0))
+        if off + fixed + payload_bytes > len(buf):
+            raise ValueError(who + f"needs more bytes than the file holds ({n} leaves, {payload_bytes} payload bytes)")
+        g = {"name": name, "transform": transform, "background": np.frombuffer(bg_raw, "<f4").copy() if has_bg else None,
+             "masks": None, "codes": None, "payload": None}
+        g["origins"] = np.frombuffer(buf, "<i4", n * 3, off).reshape(n, 3).copy(); off += 12 * n
+        g["indices"] = np.frombuffer(buf, "<u2", n * 64, off).reshape(n, 64).copy(); off += 128 * n
+        if n and int(g["indices"].max()) >= num_codes:
+            raise ValueError(who + f"holds index {int(g['indices'].max())}, out of range (num_codes {num_codes})")
+        if kind:
+            g["masks"] = np.frombuffer(buf, "<u8", n * 8, off).reshape(n, 8).copy(); off += 64 * n
+            g["codes"] = np.frombuffer(buf, "<u2", n, off).copy(); off += 2 * n
+            need = int(vec3_record_bytes(g["codes"], _vec3_popcounts(g["masks"])).sum())
+            if need != payload_bytes:
+                raise ValueError(who + f": the codes and masks need {need} payload bytes, the grid's header says {payload_bytes}")
+            g["payload"] = np.frombuffer(buf, np.uint8, payload_bytes, off).copy(); off += payload_bytes
+        grids.append(g)
+    if off != len(buf):
+        raise ValueError(f".vqv3: the headers imply {off} bytes, the file holds {len(buf)}")
+    return header, grids
+
+
+def write_vec3(path_or_buf, header: dict, grids) -> None:
+    """dumps_vec3 into a path or into an object with write()."""
+    data = dumps_vec3(header, grids)
+    if hasattr(path_or_buf, "write"):
+        path_or_buf.write(data)
+        return
+    with open(path_or_buf, "wb") as f:
+        f.write(data)
+
+
+def read_vec3(path_or_buf):
+    """loads_vec3 of a path, of bytes or of an object with read()."""
+    if isinstance(path_or_buf, (bytes, bytearray, memoryview)):
+        return loads_vec3(path_or_buf)
+    if hasattr(path_or_buf, "read"):
+        return loads_vec3(path_or_buf.read())
+    with open(path_or_buf, "rb") as f:
+        return loads_vec3(f.read())
