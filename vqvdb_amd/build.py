@@ -27,7 +27,8 @@ DEPS = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HER
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_rate.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_mask.h"),
     os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_active.h"),
-    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_file.h")]
+    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_file.h"),
+    os.path.join(os.path.dirname(HERE), "include", "vqvdb_hip_vec3_budget.h")]
 LIB = os.path.join(HERE, "libvqvdb_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-Wno-unused-value", "-Wno-unused-result"]

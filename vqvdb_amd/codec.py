@@ -160,6 +160,10 @@ VEC3_ACTIVE_SYMBOLS = ["vqhip_vec3_active_record_bytes", "vqhip_vec3_active_enco
 # every symbol include/vqvdb_hip_vec3_file.h declares (leaf-pointer calls and the .vqv3 container of the Vec3 handle; kept apart from the lists above)
 VEC3_FILE_SYMBOLS = ["vqhip_vec3_encode_leaves", "vqhip_vec3_decode_leaves", "vqhip_vec3_file_compress", "vqhip_vec3_file_compress_active",
                      "vqhip_vec3_file_decompress", "vqhip_vec3_file_info"]
+# every symbol include/vqvdb_hip_vec3_budget.h declares (byte-budget compress on compact records, in memory and into a .vqv3 file; kept
+# apart from the lists above)
+VEC3_BUDGET_SYMBOLS = ["vqhip_vec3_budget_pick", "vqhip_vec3_budget_file_bytes", "vqhip_vec3_budget_compress", "vqhip_vec3_budget_file_sweep",
+                       "vqhip_vec3_budget_file_compress"]
 VEC3_LEAF_FLOATS = 1536   # one Vec3f leaf buffer: [512][3] float32
 
 _VEC3_FULLTRAIN_I64 = ("vqhip_vec3_fulltrain_param_count", "vqhip_vec3_fulltrain_decoder_offset", "vqhip_vec3_fulltrain_aux_floats")
@@ -424,6 +428,15 @@ def load_library() -> ctypes.CDLL:
                                          ctypes.POINTER(cf), ctypes.POINTER(i64), ctypes.POINTER(i64)]
     for name in VEC3_FILE_SYMBOLS:
         getattr(lib, name).restype = ci
+    # include/vqvdb_hip_vec3_budget.h
+    lib.vqhip_vec3_budget_pick.argtypes = [vp, vp, ci, i64]
+    lib.vqhip_vec3_budget_file_bytes.argtypes = [ctypes.POINTER(_Vec3GridSource), ci, ci, vp]
+    lib.vqhip_vec3_budget_compress.argtypes = [vp, vp, vp, i64, vp, ci, i64, vp, vp, vp, vp, vp, vp, vp]
+    lib.vqhip_vec3_budget_file_sweep.argtypes = [vp, ctypes.POINTER(_Vec3GridSource), ci, vp, ci, i64, vp]
+    lib.vqhip_vec3_budget_file_compress.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(_Vec3GridSource), ci, vp, ci, i64, i64,
+                                                    ctypes.POINTER(StreamStats), vp, vp, vp]
+    for name in VEC3_BUDGET_SYMBOLS:
+        getattr(lib, name).restype = i64 if name.endswith("_bytes") else ci
     for name in VEC3_FULLTRAIN_SYMBOLS:
         if getattr(lib, name).argtypes is None:
             raise RuntimeError(f"codec.py: no argtypes declared for {name} (pointers would be truncated to 32 bits)")
@@ -1053,40 +1066,8 @@ class HipVec3Codec:
         self._check(self._lib.vqhip_vec3_decode_leaves(self._h, indices.ctypes.data, n, ptrs.ctypes.data))
 
     def _grid_sources(self, grids, need_masks: bool):
-        """(vqhip_vec3_grid_source array, its length, the arrays it points into) of the file calls' grid dicts: "name", "origins" int32
-        [n,3], "leaves" (float32 [n,512,3] or a list of n [512,3] buffers), optional "transform" (16 floats), "masks" (bool [n,512] or
-        uint64 [n,8]; required by compress_file_active) and "background" (three numbers)."""
-        n_g = len(grids)
-        src = (_Vec3GridSource * max(n_g, 1))()
-        keep = []
-        for i, g in enumerate(grids):
-            origins = np.ascontiguousarray(g["origins"], dtype=np.int32).reshape(-1, 3)
-            n = origins.shape[0]
-            leaves = g["leaves"]
-            if isinstance(leaves, np.ndarray):
-                leaves = self.check_leaves(leaves)
-                if leaves.shape[0] != n:
-                    raise ValueError(f"grid {i}: {n} origins but {leaves.shape[0]} leaves")
-                ptrs = np.ascontiguousarray(leaves.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(VEC3_LEAF_FLOATS * 4), dtype=np.uint64)
-            else:
-                ptrs = self._leaf_ptrs(leaves, n, writable=False)
-            masks = g.get("masks")
-            if masks is None and need_masks:
-                raise ValueError(f"grid {i}: compress_file_active needs masks")
-            if masks is not None:
-                masks = check_masks(pack_masks(masks) if isinstance(masks, np.ndarray) and masks.dtype == np.bool_ else masks, n)
-            tr = None if g.get("transform") is None else np.ascontiguousarray(g["transform"], dtype=np.float32).reshape(16)
-            bg = self.check_background(g.get("background"))
-            bname = g["name"].encode()
-            keep += [origins, leaves, ptrs, masks, tr, bg, bname]
-            src[i].name = bname
-            src[i].transform = None if tr is None else tr.ctypes.data
-            src[i].leaf_ptrs = ptrs.ctypes.data if n else None
-            src[i].origins = origins.ctypes.data if n else None
-            src[i].n_leaves = n
-            src[i].masks = masks.ctypes.data if masks is not None and n else None
-            src[i].background = None if bg is None else bg.ctypes.data
-        return src, n_g, keep
+        """The grid dicts of the file calls as a vqhip_vec3_grid_source array: _vec3_grid_sources."""
+        return _vec3_grid_sources(grids, need_masks)
 
     def compress_file(self, path, grids, batch_leaves: int = 0) -> dict:
         """Whole-file compress into a .vqv3 file of kind 0 (origins and the indices of encode; masks are not written).  grids: the
@@ -1105,6 +1086,57 @@ class HipVec3Codec:
         self._check(self._lib.vqhip_vec3_file_compress_active(self._h, os.fspath(path).encode(), src, n_g, tol, batch_leaves, ctypes.byref(st),
                                                               pb.ctypes.data))
         return dict(st.as_dict(), payload_bytes=[int(b) for b in pb[:n_g]])
+
+    # ---- byte budgets on compact records, in memory and into a .vqv3 file: include/vqvdb_hip_vec3_budget.h ----
+    @staticmethod
+    def check_budget(budget, what: str) -> int:
+        if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)):
+            raise TypeError(f"{what} must be an integer number of bytes, got {budget!r}")
+        if not 0 <= budget < 2**63:
+            raise ValueError(f"{what} must be in 0 .. 2^63 - 1, got {budget}")
+        return int(budget)
+
+    def rate_compress_active(self, leaves: np.ndarray, masks: np.ndarray, tols, payload_budget: int, return_leaf_err: bool = False):
+        """compress_active at the smallest of ``tols`` whose compact payload has at most ``payload_budget`` bytes
+        (vqhip_vec3_budget_compress: one model round trip with the size sweep behind it, then a decode and the encode of the selected
+        leaves only).  -> (tol_used, bytes int64 [T] as rate_sweep_active gives them, indices [n,64], leaf_code uint16 [n], payload
+        uint8 [bytes][, masked leaf_err [n,2]]), the last three or four as compress_active(leaves, masks, tol_used) returns them.
+        Raises RuntimeError if no rung fits."""
+        leaves = self.check_leaves(leaves)
+        n = leaves.shape[0]
+        masks = check_masks(masks, n)
+        tols = self.check_tols(tols)
+        payload_budget = self.check_budget(payload_budget, "payload_budget")
+        sizes, used = np.empty(len(tols), dtype=np.int64), ctypes.c_float(0)
+        idx, err = np.empty((n, 64), dtype=np.uint16), np.empty((n, VEC3_ERR_FLOATS), dtype=np.float32)
+        lc, payload, nbytes = np.empty(n, dtype=np.uint16), np.empty(n * 6144, dtype=np.uint8), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_budget_compress(self._h, leaves.ctypes.data, masks.ctypes.data, n, tols.ctypes.data, len(tols), payload_budget,
+                                                         ctypes.byref(used), sizes.ctypes.data, idx.ctypes.data, err.ctypes.data, lc.ctypes.data,
+                                                         payload.ctypes.data, ctypes.byref(nbytes)))
+        out = (used.value, sizes, idx, lc, payload[:nbytes.value].copy())
+        return out + (err,) if return_leaf_err else out
+
+    def rate_sweep_file(self, grids, tols, batch_leaves: int = 0) -> np.ndarray:
+        """-> int64 [G,T]: the payloadBytes of every grid in the file that compress_file_active writes at every rung of ``tols``
+        (per grid what rate_sweep_active gives on its leaves and masks).  Nothing is written."""
+        tols = self.check_tols(tols)
+        src, n_g, _keep = self._grid_sources(grids, need_masks=True)
+        out = np.zeros((max(n_g, 1), len(tols)), dtype=np.int64)
+        self._check(self._lib.vqhip_vec3_budget_file_sweep(self._h, src, n_g, tols.ctypes.data, len(tols), batch_leaves, out.ctypes.data))
+        return out[:n_g]
+
+    def compress_file_budget(self, path, grids, tols, file_budget: int, batch_leaves: int = 0) -> dict:
+        """compress_file_active at the smallest of ``tols`` whose FILE has at most ``file_budget`` bytes, headers, origins, indices,
+        masks and codes included (vqhip_vec3_budget_file_compress; the file has one tolerance for all grids).  Returns the stream
+        statistics with "tol_used", "payload_bytes" (one per grid) and "file_bytes".  Raises RuntimeError if no rung fits; the output
+        is then not opened and a file at ``path`` keeps its bytes."""
+        tols = self.check_tols(tols)
+        file_budget = self.check_budget(file_budget, "file_budget")
+        src, n_g, _keep = self._grid_sources(grids, need_masks=True)
+        st, pb, used, size = StreamStats(), np.zeros(max(n_g, 1), dtype=np.int64), ctypes.c_float(0), ctypes.c_int64(0)
+        self._check(self._lib.vqhip_vec3_budget_file_compress(self._h, os.fspath(path).encode(), src, n_g, tols.ctypes.data, len(tols), file_budget,
+                                                              batch_leaves, ctypes.byref(st), ctypes.byref(used), pb.ctypes.data, ctypes.byref(size)))
+        return dict(st.as_dict(), tol_used=used.value, payload_bytes=[int(b) for b in pb[:n_g]], file_bytes=size.value)
 
     def decompress_file(self, path, batch_leaves: int = 0, return_stats: bool = False):
         """Whole-file decompress of a .vqv3 file of either kind -> a list of dicts, one per grid: "name", "transform" [16], "origins"
@@ -1886,6 +1918,43 @@ class HipCodec:
         return list(out)
 
 
+def _vec3_grid_sources(grids, need_masks: bool):
+    """(vqhip_vec3_grid_source array, its length, the arrays it points into) of the file calls' grid dicts: "name", "origins" int32
+    [n,3], "leaves" (float32 [n,512,3] or a list of n [512,3] buffers), optional "transform" (16 floats), "masks" (bool [n,512] or
+    uint64 [n,8]; required by compress_file_active) and "background" (three numbers)."""
+    n_g = len(grids)
+    src = (_Vec3GridSource * max(n_g, 1))()
+    keep = []
+    for i, g in enumerate(grids):
+        origins = np.ascontiguousarray(g["origins"], dtype=np.int32).reshape(-1, 3)
+        n = origins.shape[0]
+        leaves = g["leaves"]
+        if isinstance(leaves, np.ndarray):
+            leaves = HipVec3Codec.check_leaves(leaves)
+            if leaves.shape[0] != n:
+                raise ValueError(f"grid {i}: {n} origins but {leaves.shape[0]} leaves")
+            ptrs = np.ascontiguousarray(leaves.ctypes.data + np.arange(n, dtype=np.uint64) * np.uint64(VEC3_LEAF_FLOATS * 4), dtype=np.uint64)
+        else:
+            ptrs = HipVec3Codec._leaf_ptrs(leaves, n, writable=False)
+        masks = g.get("masks")
+        if masks is None and need_masks:
+            raise ValueError(f"grid {i}: compress_file_active needs masks")
+        if masks is not None:
+            masks = check_masks(pack_masks(masks) if isinstance(masks, np.ndarray) and masks.dtype == np.bool_ else masks, n)
+        tr = None if g.get("transform") is None else np.ascontiguousarray(g["transform"], dtype=np.float32).reshape(16)
+        bg = HipVec3Codec.check_background(g.get("background"))
+        bname = g["name"].encode()
+        keep += [origins, leaves, ptrs, masks, tr, bg, bname]
+        src[i].name = bname
+        src[i].transform = None if tr is None else tr.ctypes.data
+        src[i].leaf_ptrs = ptrs.ctypes.data if n else None
+        src[i].origins = origins.ctypes.data if n else None
+        src[i].n_leaves = n
+        src[i].masks = masks.ctypes.data if masks is not None and n else None
+        src[i].background = None if bg is None else bg.ctypes.data
+    return src, n_g, keep
+
+
 def _rate_row(row) -> np.ndarray:
     r = np.asarray(row)
     if r.shape != (RATE_CLASSES,) or not np.issubdtype(r.dtype, np.integer):
@@ -1962,6 +2031,41 @@ def vec3_file_info(path) -> dict:
         raise RuntimeError(lib.vqhip_vec3_last_error(None).decode())
     return {"n_grids": ng.value, "num_codes": k.value, "kind": kind.value, "mode": mode.value, "tol": tol.value, "total_blocks": blocks.value,
             "payload_bytes": pay.value}
+
+
+def vec3_active_rate_pick(sizes, tols, budget: int) -> int:
+    """vqhip_vec3_budget_pick: the index of the smallest tols[t] by value (NaN never, of duplicates the first) with sizes[t] <=
+    ``budget``, on the int [T] that rate_sweep_active returns (or the file sizes made of them).  Raises ValueError if no rung fits."""
+    t = HipVec3Codec.check_tols(tols)
+    b = np.ascontiguousarray(sizes)
+    if b.shape != (len(t),) or not np.issubdtype(b.dtype, np.integer):
+        raise ValueError(f"{len(t)} tolerances need {len(t)} integer sizes, got shape {list(b.shape)} of {b.dtype}")
+    b = b.astype(np.int64)
+    if (b < 0).any():
+        raise ValueError("a size is negative")
+    budget = HipVec3Codec.check_budget(budget, "budget")
+    best = int(load_library().vqhip_vec3_budget_pick(b.ctypes.data, t.ctypes.data, len(t), budget))
+    if best < 0:
+        raise ValueError(f"no rung fits {budget} bytes")
+    return best
+
+
+def vec3_file_bytes(grids, kind: int, payload_bytes=None) -> int:
+    """vqhip_vec3_budget_file_bytes: the size of the .vqv3 file that compress_file (kind 0) or compress_file_active (kind 1) writes
+    for the grid dicts ``grids`` when grid g's payload has payload_bytes[g] bytes (kind 0: None).  No handle, no GPU.  Raises
+    ValueError on what the writer would refuse and on a size beyond 2^63 - 1."""
+    if kind not in (0, 1):
+        raise ValueError(f"kind must be 0 or 1, got {kind!r}")
+    src, n_g, _keep = _vec3_grid_sources(grids, need_masks=kind == 1)
+    pb = None
+    if payload_bytes is not None or kind == 1:
+        pb = np.ascontiguousarray(payload_bytes if payload_bytes is not None else [], dtype=np.int64).reshape(-1)
+        if len(pb) != n_g:
+            raise ValueError(f"{n_g} grids need {n_g} payload sizes, got {len(pb)}")
+    size = int(load_library().vqhip_vec3_budget_file_bytes(src, n_g, int(kind), None if pb is None else pb.ctypes.data))
+    if size < 0:
+        raise ValueError("the writer would refuse these grids or payload sizes, or the file's size passes 2^63 - 1")
+    return size
 
 
 class HipMultiCodec:

@@ -2615,5 +2615,6 @@ int vqhip_selftest_mfma(vqhip_codec* c, int64_t* mismatches)
 #include "vq_vec3_mask.inc"
 #include "vq_vec3_active.inc"
 #include "vq_vec3_file.inc"
+#include "vq_vec3_budget.inc"
 #include "vq_vec3_train.inc"
 #include "vq_vec3_fulltrain.inc"

@@ -2,7 +2,9 @@
 // _file_compress_active, _file_decompress, _file_info; include/vqvdb_hip_vec3_file.h, DESIGN.md §26).  Part of vq_runtime.hip's
 // translation unit, after vq_vec3_active.inc.  No kernel of its own: a batch is gathered into pinned staging and handed to the chunk
 // functions of the in-memory calls (v3_encode_host_chunk, v3_decode_host_chunk, v3a_compress_chunk, v3a_decompress_chunk), and the
-// container is vq_vec3_file_format.h's.  Chunked and serial: gather, GPU work and file I/O of a batch follow one another.
+// container is vq_vec3_file_format.h's.  Chunked and serial: gather, GPU work and file I/O of a batch follow one another.  The writer
+// (v3f_compress) takes the function that fills a batch's indices, codes and records as a parameter: V3fModelBatch here, pass 2 of the
+// byte-budget call in vq_vec3_budget.inc.
 
 #include "../../include/vqvdb_hip_vec3_file.h"
 #include "vq_vec3_file_format.h"
@@ -44,12 +46,34 @@ int64_t v3f_step(const vqhip_vec3_codec* c, int64_t batch_leaves) { return batch
 
 const char* v3f_mode_name(int mode) { return mode == VQHIP_VEC3_PRECISION_BF16 ? "bf16" : "fp32"; }
 
-// kind 0 (tol unused) or kind 1 of the compress; the partial output is the caller's to remove when this fails.  vqhip_stream_stats
-// has one field for file I/O, read_s ("file read/write"): here it collects the time of the writes, copy_s that of the gathers.
-int v3f_compress(vqhip_vec3_codec* c, vqv3f::File& f, const vqhip_vec3_grid_source* grids, int n_grids, int kind, float tol, int64_t batch_leaves,
-                 vqhip_stream_stats& st, int64_t* payload_bytes)
+// a batch of the compress by the model: the leaves o .. o + m of grid G gathered into the pinned stage, then the chunk function of
+// the in-memory call of that kind.  The batch functions of v3f_compress fill idx [m][64] and, kind 1, code [m] and the batch's records
+// from payload on, *bytes their size; the time of their gathers goes to st.copy_s.
+struct V3fModelBatch {
+    vqhip_vec3_codec* c;
+    const char* what;
+    int kind;
+    float tol;
+    vqhip_stream_stats& st;
+    int operator()(int, const vqhip_vec3_grid_source& G, int64_t o, int64_t m, uint16_t* idx, uint16_t* code, uint8_t* payload, int64_t* bytes) const
+    {
+        if (int rc = v3f_check_ptrs(c, what, G.leaf_ptrs + o, m)) return rc;
+        if (int rc = v3f_ensure_stage(c, m)) return rc;
+        const double t = now_s();
+        v3f_gather(c->fl_stage, G.leaf_ptrs + o, m);
+        st.copy_s += now_s() - t;
+        if (kind) return v3a_compress_chunk(c, what, c->fl_stage, G.masks + o * 8, m, tol, idx, nullptr, code, payload, bytes);
+        return v3_encode_host_chunk(c, c->fl_stage, m, idx);
+    }
+};
+
+// kind 0 (tol unused) or kind 1 of the compress, every batch's indices, codes and records from `batch`; the partial output is the
+// caller's to remove when this fails.  vqhip_stream_stats has one field for file I/O, read_s ("file read/write"): here it collects
+// the time of the writes, copy_s that of the gathers.
+template <typename Batch>
+int v3f_compress(vqhip_vec3_codec* c, const char* what, vqv3f::File& f, const vqhip_vec3_grid_source* grids, int n_grids, int kind, float tol,
+                 int64_t batch_leaves, vqhip_stream_stats& st, int64_t* payload_bytes, const Batch& batch)
 {
-    const char* what = kind ? "vec3 compress_file_active" : "vec3 compress_file";
     const std::string wfail = std::string(what) + ": failed to write to the .vqv3 file";
     if (int rc = v3_prepare(c)) return rc;
     vqv3f::Header h;
@@ -80,11 +104,6 @@ int v3f_compress(vqhip_vec3_codec* c, vqv3f::File& f, const vqhip_vec3_grid_sour
         int64_t total = 0;   // the grid's payload bytes so far
         for (int64_t o = 0; o < n; o += step) {
             const int64_t m = std::min(step, n - o);
-            if (int rc = v3f_check_ptrs(c, what, G.leaf_ptrs + o, m)) return rc;
-            if (int rc = v3f_ensure_stage(c, m)) return rc;
-            t = now_s();
-            v3f_gather(c->fl_stage, G.leaf_ptrs + o, m);
-            st.copy_s += now_s() - t;
             idx.resize((size_t)m * 64);
             int64_t bytes = 0;
             if (kind) {
@@ -94,11 +113,8 @@ int v3f_compress(vqhip_vec3_codec* c, vqv3f::File& f, const vqhip_vec3_grid_sour
                     payload_leaves = payload ? m : 0;
                     if (!payload) return v3_fail(c, VQHIP_ERR_NOMEM, std::string(what) + ": cannot allocate the payload buffer of " + std::to_string(m) + " leaves");
                 }
-                if (int rc = v3a_compress_chunk(c, what, c->fl_stage, G.masks + o * 8, m, tol, idx.data(), nullptr, code.data(), payload.get(), &bytes))
-                    return rc;
-            } else if (int rc = v3_encode_host_chunk(c, c->fl_stage, m, idx.data())) {
-                return rc;
             }
+            if (int rc = batch(g, G, o, m, idx.data(), code.data(), payload.get(), &bytes)) return rc;
             t = now_s();
             bool ok = f.write_at(M.origins_at + 12 * (uint64_t)o, G.origins + 3 * o, 12 * (uint64_t)m) &&
                       f.write_at(M.indices_at + 128 * (uint64_t)o, idx.data(), 128 * (uint64_t)m);
@@ -119,11 +135,11 @@ int v3f_compress(vqhip_vec3_codec* c, vqv3f::File& f, const vqhip_vec3_grid_sour
     return VQHIP_OK;
 }
 
-int v3f_compress_file(vqhip_vec3_codec* c, const char* path, const vqhip_vec3_grid_source* grids, int n_grids, int kind, float tol,
-                      int64_t batch_leaves, vqhip_stream_stats* stats, int64_t* payload_bytes)
+// what a compress refuses of its path and grid list before anything is opened or launched (path NULL: a call without an output)
+int v3f_check_grids(vqhip_vec3_codec* c, const std::string& what, bool need_path, const char* path, const vqhip_vec3_grid_source* grids, int n_grids,
+                    int kind)
 {
-    const std::string what = kind ? "vec3 compress_file_active" : "vec3 compress_file";
-    if (!path || !grids) return v3_fail(c, VQHIP_ERR_INVALID, what + ": null path or grid list");
+    if ((need_path && !path) || !grids) return v3_fail(c, VQHIP_ERR_INVALID, what + ": null path or grid list");
     if (n_grids < 1 || n_grids > 255) return v3_fail(c, VQHIP_ERR_INVALID, what + ": a .vqv3 file holds 1..255 grids");
     for (int g = 0; g < n_grids; ++g) {
         const vqhip_vec3_grid_source& G = grids[g];
@@ -131,17 +147,32 @@ int v3f_compress_file(vqhip_vec3_codec* c, const char* path, const vqhip_vec3_gr
             return v3_fail(c, VQHIP_ERR_INVALID, what + ": grid " + std::to_string(g) + " has no name, no leaves/origins or more than 2^32-1 leaves");
         if (kind && G.n_leaves > 0 && !G.masks) return v3_fail(c, VQHIP_ERR_INVALID, what + ": grid " + std::to_string(g) + " has no masks");
     }
+    return VQHIP_OK;
+}
+
+// the output opened, written by v3f_compress, closed, and removed if any of that failed
+template <typename Batch>
+int v3f_write_file(vqhip_vec3_codec* c, const char* what, const char* path, const vqhip_vec3_grid_source* grids, int n_grids, int kind, float tol,
+                   int64_t batch_leaves, vqhip_stream_stats& st, int64_t* payload_bytes, const Batch& batch)
+{
+    vqv3f::File f;
+    if (!f.open_write(path)) return v3_fail(c, VQHIP_ERR_INVALID, std::string("Cannot open output file: ") + path);
+    int rc = v3f_compress(c, what, f, grids, n_grids, kind, tol, batch_leaves, st, payload_bytes, batch);
+    if (!f.close() && !rc) rc = v3_fail(c, VQHIP_ERR_INVALID, std::string(what) + ": error closing the output file");
+    if (rc) std::remove(path);   // no partial output
+    return rc;
+}
+
+int v3f_compress_file(vqhip_vec3_codec* c, const char* path, const vqhip_vec3_grid_source* grids, int n_grids, int kind, float tol,
+                      int64_t batch_leaves, vqhip_stream_stats* stats, int64_t* payload_bytes)
+{
+    const char* what = kind ? "vec3 compress_file_active" : "vec3 compress_file";
+    if (int rc = v3f_check_grids(c, what, true, path, grids, n_grids, kind)) return rc;
     const double t_start = now_s();
     vqhip_stream_stats st;
     std::memset(&st, 0, sizeof st);
-    vqv3f::File f;
-    if (!f.open_write(path)) return v3_fail(c, VQHIP_ERR_INVALID, std::string("Cannot open output file: ") + path);
-    int rc = v3f_compress(c, f, grids, n_grids, kind, tol, batch_leaves, st, payload_bytes);
-    if (!f.close() && !rc) rc = v3_fail(c, VQHIP_ERR_INVALID, what + ": error closing the output file");
-    if (rc) {
-        std::remove(path);   // no partial output
+    if (int rc = v3f_write_file(c, what, path, grids, n_grids, kind, tol, batch_leaves, st, payload_bytes, V3fModelBatch{c, what, kind, tol, st}))
         return rc;
-    }
     st.wall_s = now_s() - t_start;
     if (stats) *stats = st;
     return VQHIP_OK;

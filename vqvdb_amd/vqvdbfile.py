@@ -382,6 +382,34 @@ def loads_vec3(buf):
     return header, grids
 
 
+def vec3_file_bytes(grids, kind: int, payload_bytes=None) -> int:
+    """len(dumps_vec3(...)) without the data: 24 + sum_g (102 + nameLength_g + n_g (12 + 128 + (64 + 2 if kind 1))) + sum_g
+    payload_bytes[g].  grids: dicts with "name" and "origins" [n,3] (or "n_leaves"); payload_bytes: one integer per grid for kind 1,
+    None (or zeros) for kind 0.  Restates vqhip_vec3_budget_file_bytes of include/vqvdb_hip_vec3_budget.h."""
+    if kind not in (VEC3_KIND_INDICES, VEC3_KIND_ACTIVE):
+        raise ValueError(f".vqv3: kind {kind} is neither 0 nor 1")
+    if not 1 <= len(grids) <= 255:
+        raise ValueError("a .vqv3 file holds 1..255 grids")
+    if payload_bytes is None:
+        if kind:
+            raise ValueError(".vqv3: a file of kind 1 needs every grid's payload bytes")
+        payload_bytes = [0] * len(grids)
+    if len(payload_bytes) != len(grids):
+        raise ValueError(f"{len(grids)} grids but {len(payload_bytes)} payload sizes")
+    total = VEC3_HEADER_BYTES
+    for g, payload in zip(grids, payload_bytes):
+        n = int(g["n_leaves"]) if "n_leaves" in g else len(np.asarray(g["origins"]).reshape(-1, 3))
+        name = g["name"].encode() if isinstance(g["name"], str) else bytes(g["name"])
+        if not 0 <= n < 1 << 32:
+            raise ValueError("more than 2^32-1 leaves in one grid")
+        if int(payload) < 0 or (not kind and int(payload)):
+            raise ValueError(".vqv3: a payload size is negative, or not zero in a file of kind 0")
+        total += 102 + len(name) + n * (12 + 128 + (64 + 2 if kind else 0)) + int(payload)
+    if total >= 1 << 63:
+        raise ValueError(".vqv3: the file's size passes 2^63 - 1")
+    return total
+
+
 def write_vec3(path_or_buf, header: dict, grids) -> None:
     """dumps_vec3 into a path or into an object with write()."""
     data = dumps_vec3(header, grids)
